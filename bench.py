@@ -3,21 +3,35 @@
 N_obj in [1,128] packed by batching_helpers, batch 64 per GPU (configs[1]); frames shard across ranks with
 no data-path collective.  Two scaling modes, both built from accvlab.draw_heatmap.sharding:
   weak   (default, `value`): every rank draws its OWN 64-frame batch (seed 42 + rank) — per-GPU work is fixed;
-  strong (`--scaling strong`, and `secondary.strong_scaling` of every weak run): the ONE 64-frame batch of seed 42 is cut with
-         `shard_range` into 64 / 32 / 16 / 8 frames per GPU at 1 / 2 / 4 / 8 GPUs.
+  strong (`--scaling strong`, and `secondary.strong_scaling` of a `--full` weak run on N > 1 GPUs): the ONE 64-frame
+         batch of seed 42 is cut with `shard_range` into 64 / 32 / 16 / 8 frames per GPU at 1 / 2 / 4 / 8 GPUs
+         (SURVEY §8e, config C4).
 
 One "step" = one fused clear+draw of the whole batch through the public operator
 ``accvlab.draw_heatmap.draw_heatmap_batched(..., clear=True)`` -> C-ABI -> one HIP kernel launch, with the
 object lists already resident in HBM.  Prints ONE JSON line on rank 0.
 
     python bench.py --gpus 1 --steps 500 --warmup 50
+    python bench.py --gpus 1 --steps 500 --warmup 50 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the optional output dump and the
+line.  Its `roofline` comes from the HIP events of the timed region and needs no launch of its own.  `--full` adds every
+side measurement: kernel times of spaced launches, the §8(d) work counters, the box's clock / power state, the rule-B
+and in-place rates, the strong split (measured at N > 1, predicted from one GPU at N = 1), configs[0] / [2] / [3] and
+the CPU baselines (all cores and one core).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed (the heat maps a caller of
+`draw_heatmap_batched` receives) as DIR/*.npy: the whole first frame, the sum of every frame, and the values at a fixed
+seeded sample of positions of the whole batch, with those positions.  The inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
+
 The line is self-certifying: `roofline.kernel` is the dispatch string the library reports for the launches that were
 timed, `roofline.achieved` comes from HIP events on the launch stream inside this run, `roofline.traffic` is only
-quoted from a committed PMC profile of THE SAME kernel instantiation (else null), and the §8(d) work counters, the
-rule-B and in-place rates and the CPU baselines (all cores and one core) are measured in this run.
+quoted from a committed PMC profile of THE SAME kernel instantiation (else null), and everything `--full` adds is
+measured in that run.
 The multi-rank control flow (rank layout, per-rank seeds, barrier-bracketed timed region, MAX over ranks) lives in
 accvlab.draw_heatmap.sharding and is exercised on two gloo ranks by tests/test_sharding_gloo.py.
 """
@@ -39,6 +53,8 @@ import torch  # noqa: E402
 import bench_workloads as wl  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters)
+DUMP_SAMPLE = 1 << 21   # positions of the seeded sample --dump-outputs takes of the batch (8 MB of values + 16 MB of positions)
+DUMP_SEED = 0
 # v_exp_f32 issues one wave64 instruction per 8 cycles per SIMD (same guide, "vector-instruction ISSUE cost"):
 # 256 CUs x 4 SIMDs x 64 lanes / 8 cycles x 2.4 GHz
 EXP_PEAK_PER_S = 256 * 4 * 64 / 8 * 2.4e9
@@ -230,6 +246,28 @@ def per_launch_kernel_ms(nat, step, steps, sync):
                            "than a back-to-back one — not the roofline figure" % steps)
 
 
+def dump_outputs(out_dir, hm):
+    """The heat maps [frames, H, W] of the last timed step, in under 64 MB: frame 0 whole, the float64 sum of every frame,
+    and the values at DUMP_SAMPLE positions of the flattened batch drawn by a generator of fixed seed (the same positions
+    for the same --batch, whatever the build)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = hm.reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        pos = torch.arange(flat.numel(), dtype=torch.int64)
+    else:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SEED)
+        pos = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+    arrays = {"heatmap_frame0": hm[0].float(),
+              "heatmap_frame_sums": hm.sum(dim=(1, 2), dtype=torch.float64),
+              "heatmap_sample": flat[pos.to(hm.device)].float(),
+              "heatmap_sample_positions": pos.to(torch.float64)}      # flat index into [frames, H, W]; exact below 2^53
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -239,11 +277,18 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU")
     ap.add_argument("--rule", default="A", choices=["A", "B"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
-                    help="which mode `value` reports; the other one is carried in `secondary`")
-    ap.add_argument("--no-configs", action="store_true", help="skip configs[0] / [2] / [3] (secondary.configs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the rule-B / in-place / zero-fill side measurements")
+                    help="which mode `value` reports; `secondary` carries the weak one, and with --full the other one")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (see the module docstring); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32 / float64, < 64 MB)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip configs[0] / [2] / [3] (secondary.configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the rule-B / in-place / zero-fill side measurements")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.batch < 1:
+        ap.error("--steps and --batch must be >= 1 and --warmup >= 0")
 
     from accvlab.draw_heatmap import sharding
 
@@ -285,7 +330,7 @@ def main():
     # reports its sample)
     for _ in range(300):
         step()
-    env = device_env(dev_index)
+    env = device_env(dev_index) if args.full else None
     # extra untimed pre-warm: the chip needs ~15 ms of back-to-back launches after an idle/sync before kernel times
     # settle (profiles/r01_rocprof: 109 -> 128 -> 97 us); keep the queue full for >= 100 ms right up to the timed region
     sync()
@@ -317,13 +362,18 @@ def main():
     region_ms = e0.elapsed_time(e1) / args.steps
     kern_ms = e_first.elapsed_time(e1) / (args.steps - 1) if args.steps > 1 else region_ms
     kernel = nat.last_dispatch()
-    # for information: the same kernel timed launch by launch with start/stop events on the kernel itself (hipExtLaunchKernel
-    # through accv_draw_heatmap_time_next_launch), K further launches behind the timed region.  Those events cost ~4 us of
-    # dispatch each, so the launches are SPACED — and a spaced launch runs 3-4 % faster than a back-to-back one (rocprofv3 shows
-    # the same split: profiles/r02_rocprof).  The roofline entry stays on the back-to-back figure, i.e. on what a step costs.
-    trace_index["spaced_first_launch"] = launches[0] + 150     # per_launch_kernel_ms refills the queue with 150 launches first
-    trace_index["spaced_launches"] = args.steps
-    isolated_ms, isolated_note = per_launch_kernel_ms(nat, step, args.steps, sync)
+    use_strong = args.scaling == "strong"
+    if args.dump_outputs and rank == 0 and not use_strong:
+        dump_outputs(args.dump_outputs, hm)
+    if args.full:
+        # for information: the same kernel timed launch by launch with start/stop events on the kernel itself
+        # (hipExtLaunchKernel through accv_draw_heatmap_time_next_launch), K further launches behind the timed region.  Those
+        # events cost ~4 us of dispatch each, so the launches are SPACED — and a spaced launch runs 3-4 % faster than a
+        # back-to-back one (rocprofv3 shows the same split: profiles/r02_rocprof).  The roofline entry stays on the
+        # back-to-back figure, i.e. on what a step costs.
+        trace_index["spaced_first_launch"] = launches[0] + 150     # per_launch_kernel_ms refills the queue with 150 launches
+        trace_index["spaced_launches"] = args.steps
+        isolated_ms, isolated_note = per_launch_kernel_ms(nat, step, args.steps, sync)
     red_dev = dev if backend == "nccl" else None
     wall_ms = sharding.max_over_ranks(wall_ms, device=red_dev)
     kern_ms = sharding.max_over_ranks(kern_ms, device=red_dev)
@@ -339,23 +389,27 @@ def main():
         return c, r, int(sum(int(x.shape[0]) for x in rl))
 
     strong_buf = []
+    strong_views = []     # the maps each strong step draws into (the last one is what the timed strong steps computed)
 
     def strong_step(begin, end):
         c, r, _ = strong_inputs(begin, end)
         if hm.shape[0] < end - begin and (not strong_buf or strong_buf[0].shape[0] < end - begin):
             strong_buf[:] = [torch.empty((end - begin, H, W), dtype=torch.float32, device=dev)]   # --batch below the shard size
         view = (hm if hm.shape[0] >= end - begin else strong_buf[0])[: end - begin]
+        strong_views.append(view)
         return lambda: draw_heatmap_batched(view, c, r, 6.0, 1.0, clear=True)
 
     strong = None
-    if world > 1 or args.scaling == "strong":
+    if use_strong or (args.full and world > 1):
         strong = sharding.strong_scaling_run(strong_step, STRONG_TOTAL, rank, world, args.steps, args.warmup + 300,
                                              dist=dist, sync=sync, device=red_dev)
         strong["kernel"] = nat.last_dispatch()
+        if args.dump_outputs and rank == 0 and use_strong:
+            dump_outputs(args.dump_outputs, strong_views[-1])
 
     # secondary, rank 0 only: rule B, the reference's exact in-place semantics, and the streaming-write ceiling
     extra = {}
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and args.full and not args.no_secondary:
         def timed(fn, iters=50, warm=20):
             for _ in range(warm):
                 fn()
@@ -401,7 +455,7 @@ def main():
                         "achieved_GBps": b_in_bytes / ms_b_in / 1e6},
             "clipped_area_sum_per_frame": wc_b["clipped_area_sum_per_frame"], "tiles_touched": wc_b["tiles_touched"]}
 
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         # what a shard of the strong split costs on ONE GPU (all shards of each split, slowest one counts): predicts the
         # strong curve the driver measures — an 8-frame launch is 66 MB of map, i.e. store stream + launch boundary
         def shard_ms(begin, end, iters=200, warm=100):
@@ -429,7 +483,7 @@ def main():
         extra["strong_scaling_prediction_from_one_gpu"] = {
             "splits": pred, "note": "each shard of the seed-42 64-frame batch drawn back to back on this GPU (HIP events, 200 "
                                     "launches); N ranks run their shards concurrently, so the job takes the slowest shard's time"}
-    if rank == 0 and world == 1 and not args.no_secondary and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and not args.no_configs:
         import bench_configs
 
         t_cfg = time.perf_counter()
@@ -445,19 +499,11 @@ def main():
     alg_bytes = B * H * W * 4 + 12 * n_objects + 4 * B  # H*W*4 + 12*N_i + 4 per frame
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
     traffic, traffic_source = committed_traffic(kernel, B)
-    tile_h = 32 if "R=16" in kernel else 16
-    wc = work_counters(centers_l, radii_l, 128, tile_h)
-    # exp evaluations of the tile kernel: per (tile, hit) one row-factor table entry per tile row + 4 column factors per lane
-    exps = wc["tile_hits_total"] * (tile_h + 256)
-    wc["exp_evaluations_per_launch"] = exps
-    wc["transcendental_ceiling"] = {"peak_exp_per_s": EXP_PEAK_PER_S, "min_ms_per_launch": exps / EXP_PEAK_PER_S * 1e3,
-                                    "fraction_of_kernel_time": exps / EXP_PEAK_PER_S * 1e3 / kern_ms}
     weak = {"frames_per_s": sharding.job_throughput(B, world, wall_ms), "ms_per_step": wall_ms, "frames_per_rank": B,
             "total_frames": B * world}
     if strong is not None:
         extra["strong_scaling"] = strong
     extra["weak_scaling"] = weak
-    use_strong = args.scaling == "strong"
     out = {
         "metric": "heatmap frames/sec (1920x1080 fp32, ragged N_obj in [1,128], fused clear+draw)",
         "value": strong["frames_per_s"] if use_strong else weak["frames_per_s"],
@@ -492,14 +538,23 @@ def main():
                      "kernel_ms_source": "HIP events on the launch stream inside the timed region: end of launch 1 -> end of "
                                          "launch K, divided by K - 1 (back-to-back launches)",
                      "timed_region_event_ms_per_step": region_ms,
-                     "kernel_ms_spaced_launches": isolated_ms, "kernel_ms_spaced_launches_note": isolated_note,
                      "trace_index": trace_index},
-        "work": wc,
         "secondary": extra,
-        "device": env or {},
     }
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(centers_l, radii_l, B)
+    if args.full:
+        out["roofline"]["kernel_ms_spaced_launches"] = isolated_ms
+        out["roofline"]["kernel_ms_spaced_launches_note"] = isolated_note
+        tile_h = 32 if "R=16" in kernel else 16
+        wc = work_counters(centers_l, radii_l, 128, tile_h)
+        # exp evaluations of the tile kernel: per (tile, hit) one row-factor table entry per tile row + 4 column factors per lane
+        exps = wc["tile_hits_total"] * (tile_h + 256)
+        wc["exp_evaluations_per_launch"] = exps
+        wc["transcendental_ceiling"] = {"peak_exp_per_s": EXP_PEAK_PER_S, "min_ms_per_launch": exps / EXP_PEAK_PER_S * 1e3,
+                                        "fraction_of_kernel_time": exps / EXP_PEAK_PER_S * 1e3 / kern_ms}
+        out["work"] = wc
+        out["device"] = env or {}
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(centers_l, radii_l, B)
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
