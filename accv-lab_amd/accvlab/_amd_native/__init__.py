@@ -11,7 +11,8 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# ACCV_HIP_LIB points experiments (scripts/h1_variants.py) at another build, e.g. the A/B build `make tune`
+# ACCV_HIP_LIB points experiments at another build of the library, e.g. one made by scripts/build_prev_lib.sh or
+# scripts/build_variant_lib.sh
 # ACCV_NO_HOST_FASTPATH=1: the operators keep to their python formulation (the C++ host fast paths of draw_heatmap_batched,
 # the ragged gather / scatter and the lane sampler decline everything) — used to run the test-suite over both
 NO_HOST_FASTPATH = os.environ.get("ACCV_NO_HOST_FASTPATH", "") not in ("", "0")
@@ -100,10 +101,6 @@ SIGNATURES = {
     "accv_polyline_sample_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i]),
     "accv_polyline_sample_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
-# not in the public header and not in the shipped library: the knob setter of the A/B build (make -C csrc tune)
-_PRIVATE = {
-    "accv_tune_set": (_i, [ctypes.c_char_p, _i]),
-}
 
 _lib = None
 _handle = None
@@ -147,7 +144,7 @@ class _Lib:
 
     def __getattr__(self, name):
         fn = getattr(self._ctypes, name)
-        sig = SIGNATURES.get(name) or _PRIVATE.get(name)
+        sig = SIGNATURES.get(name)
         fast = _fast_entry(fn, *sig) if sig and name not in _BLOCKING else None
         fn = fast or fn
         setattr(self, name, fn)       # cached: __getattr__ is not consulted again
@@ -168,13 +165,10 @@ def lib() -> "_Lib":
                 "(run `make -C accv-lab_amd/csrc` or __graft_entry__.build()). There is no CPU fallback."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, _PRIVATE):
-            for name, (res, args) in table.items():
-                if table is _PRIVATE and not hasattr(handle, name):
-                    continue
-                fn = getattr(handle, name)
-                fn.restype = res
-                fn.argtypes = args
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
         _handle = handle
         _lib = _Lib(handle)
     return _lib
@@ -190,15 +184,6 @@ def check(status: int, what: str = "") -> None:
     if status != OK:
         msg = lib().accv_last_error()
         raise AccvNativeError(f"{what}: {msg.decode() if msg else 'error'} (status {status})")
-
-
-def tune_set(key: str, value: int) -> None:
-    """Kernel-variant knobs exist only in the A/B build (``make -C accv-lab_amd/csrc tune`` + ``ACCV_HIP_LIB``)."""
-    handle = ctypes_lib()
-    if not hasattr(handle, "accv_tune_set"):
-        raise AccvNativeError("this libaccv_hip.so has no tuning knobs (shipped build); use the public flags "
-                              "(tile_rows=, write_through=, small_radii=) or load the A/B build via ACCV_HIP_LIB")
-    check(handle.accv_tune_set(key.encode(), int(value)), "accv_tune_set")
 
 
 def last_dispatch() -> str:

@@ -34,18 +34,16 @@
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "accv_common.h"
 #include "polyline_arith.h"
 
-#ifndef ACCV_BOX_TILE_R
-#define ACCV_BOX_TILE_R 8   // rows per half-wave of a box-map tile (multi-scale launches): 128 x 16 pixel tiles.  4 = 128 x 8 tiles
-                            // (54 VGPRs, 8 waves per SIMD, twice the waves): box maps of config 3 17.1 -> 18.4 us, measured
-#endif
-
 namespace {
 
 constexpr int kWavesPerGroup = 1;  // 1 wave per workgroup measured 6.5 % faster than 4 (profiles/r01_h1_variants_wpg.log)
+constexpr int kBoxTileR = 8;  // rows per half-wave of a box-map tile (multi-scale launches): 128 x 16 pixel tiles.  4 = 128 x 8 tiles
+                              // (54 VGPRs, 8 waves per SIMD, twice the waves): box maps of config 3 17.1 -> 18.4 us, measured
 constexpr int kCand = 64;  // candidates per cull round = one per lane
 constexpr float kLog2e = 1.4426950408889634f;
 
@@ -444,7 +442,7 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
     // are covered about once or more rewrite most of their tiles -> write-through non-temporal stores (sc1 nt: -6 % on
     // the dense rule-A batch); sparse planes touch a few tiles that the next consumer finds in L2 / Infinity Cache ->
     // plain stores (write-through costs them 27 %, profiles/r01_h1_ab_rows_store_policy.log).  Same values either way.
-    bool write_through = SM == 2 || SM == 4;
+    bool write_through = SM == 4;
     if constexpr (SM == 5 && PX == 4) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) cover += __shfl_xor(cover, d);
@@ -460,14 +458,11 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
             out = V{acc[i][0], acc[i][1], acc[i][2], acc[i][3]};  // in-place mode: acc already holds max(old, splats)
         else
             out = acc[i][0];
-        if constexpr (SM == 1) {
-            __builtin_nontemporal_store(out, dst);
-        } else if constexpr (SM >= 2 && PX == 4) {
-            // write-through (sc1) / write-through non-temporal (sc1 nt) 16-byte buffer store
-            constexpr int aux = SM == 2 ? 16 : 18;  // sc1 | sc1+nt
+        if constexpr (SM >= 4 && PX == 4) {
+            // write-through non-temporal (sc1 nt) 16-byte buffer store
             if (write_through) {
                 const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(plane_ptr, 0, (int)((size_t)p.H * p.W * 4), 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(out, rsrc, (int)(((size_t)row * p.W + col0) * 4), 0, aux);
+                __builtin_amdgcn_raw_buffer_store_b128(out, rsrc, (int)(((size_t)row * p.W + col0) * 4), 0, 18);   // sc1 | nt
             } else {
                 *dst = out;
             }
@@ -544,7 +539,7 @@ __global__ __launch_bounds__(64) void splat_multi_kernel(const MultiParams mp)
     const int s = scale_of_group(mp, blockIdx.x, first);
     // (the scale's parameters are NOT requested up front here, neither as copies (preload_params) nor as asm inputs: either way
     // the register-bound tile body goes from 79 to 85-124 VGPRs and loses one or two waves per SIMD)
-    splat_body<4, ACCV_BOX_TILE_R, CLEAR, SM, 1, 1>(mp.scale[s], (long long)blockIdx.x - first);
+    splat_body<4, kBoxTileR, CLEAR, SM, 1, 1>(mp.scale[s], (long long)blockIdx.x - first);
 }
 
 // ---------------------------------------------------------------- small splats (lane rasters, point-like targets)
@@ -728,7 +723,7 @@ __device__ __forceinline__ Cand group_candidates(const TileCtx& t, const PixelSc
 template <int SM>
 __device__ __forceinline__ void store_segment(const SplatParams& p, float* plane_ptr, int row, int col0, const vfloat4& v)
 {
-    if constexpr (SM >= 2) {
+    if constexpr (SM == 4) {
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(plane_ptr, 0, (int)((size_t)p.H * p.W * 4), 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (int)(((size_t)row * p.W + col0) * 4), 0, 18);
     } else {
@@ -1353,7 +1348,7 @@ __global__ __launch_bounds__(64) void splat_multi_sampler_kernel(const TargetsPa
     const long long group = (long long)blockIdx.x - tp.sp.n_polylines;
     long long first;
     const int s = scale_of_group(tp.mp, group, first);
-    splat_body<4, ACCV_BOX_TILE_R, CLEAR, SM, 1, 1>(tp.mp.scale[s], group - first);
+    splat_body<4, kBoxTileR, CLEAR, SM, 1, 1>(tp.mp.scale[s], group - first);
 }
 
 // bounding box (xmin, ymin, xmax, ymax) of every 64 consecutive points of points[b, :, :] (NaN points ignored; a group
@@ -1416,8 +1411,24 @@ inline void launch_maybe_timed(K kernel, const dim3& grid, const dim3& block, hi
     else
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, p);
 }
+// the run-time (clear, write-through) pair as compile-time constants: f(std::bool_constant<CLEAR>{}, std::integral_constant<int,
+// SM>{}) with SM = 4 (write-through non-temporal stores) or 0 (plain stores)
+template <class F>
+void with_variant(bool clear, bool write_through, F&& f)
+{
+    using Plain = std::integral_constant<int, 0>;
+    using WriteThrough = std::integral_constant<int, 4>;
+    if (clear && write_through)
+        f(std::true_type{}, WriteThrough{});
+    else if (clear)
+        f(std::true_type{}, Plain{});
+    else if (write_through)
+        f(std::false_type{}, WriteThrough{});
+    else
+        f(std::false_type{}, Plain{});
+}
 
-int launch_splat_small(SplatParams p, long long planes, bool clear, int sm, hipStream_t stream, const LaunchEvents& ev)
+int launch_splat_small(SplatParams p, long long planes, bool clear, bool write_through, hipStream_t stream, const LaunchEvents& ev)
 {
     p.tiles_x = (p.W + 127) / 128;
     p.tiles_y = (p.H + 15) / 16;
@@ -1431,18 +1442,10 @@ int launch_splat_small(SplatParams p, long long planes, bool clear, int sm, hipS
         if (p.n_tiles > INT_MAX) return accv::fail(ACCV_EINVAL, "draw_heatmap: %lld tiles exceed the grid limit", p.n_tiles);
         grid = dim3((unsigned)p.n_tiles);
     }
-    if (clear) {
-        if (sm >= 2)
-            launch_maybe_timed(splat_small_kernel<true, 4>, grid, dim3(64), stream, ev, p);
-        else
-            launch_maybe_timed(splat_small_kernel<true, 0>, grid, dim3(64), stream, ev, p);
-    } else {
-        if (sm >= 2)
-            launch_maybe_timed(splat_small_kernel<false, 4>, grid, dim3(64), stream, ev, p);
-        else
-            launch_maybe_timed(splat_small_kernel<false, 0>, grid, dim3(64), stream, ev, p);
-    }
-    note_dispatch("splat_small_kernel", 4, 8, clear, sm >= 2 ? 4 : 0, grid, dim3(64));
+    with_variant(clear, write_through, [&](auto CL, auto SM) {
+        launch_maybe_timed(splat_small_kernel<CL, SM>, grid, dim3(64), stream, ev, p);
+    });
+    note_dispatch("splat_small_kernel", 4, 8, clear, write_through ? 4 : 0, grid, dim3(64));
     return accv::check_launch("draw_heatmap small-splat kernel");
 }
 
@@ -1598,56 +1601,33 @@ __global__ void fill_tail_kernel(float* __restrict__ dst, size_t n, float value)
     if (i < n) dst[i] = value;
 }
 
-// store mode SM: 0 plain, 4 write-through non-temporal (sc1 nt).  (The A/B build also instantiates 1 = non-temporal and
-// 2 = write-through, and 4-wave workgroups: -DACCV_TUNE_BUILD.)
-template <int PX, int R, int WPG = kWavesPerGroup>
+// store mode sm: 0 plain, 4 write-through non-temporal (sc1 nt), 5 density-adaptive (in-place launches only: a fused-clear
+// launch asking for it gets plain stores).  PX == 1 has plain stores only.
+template <int PX, int R>
 int launch_splat(SplatParams p, long long planes, bool clear, int sm, hipStream_t stream, const LaunchEvents& ev)
 {
     p.tiles_x = (p.W + 32 * PX - 1) / (32 * PX);
     p.tiles_y = (p.H + 2 * R - 1) / (2 * R);
     p.n_tiles = planes * p.tiles_x * p.tiles_y;
     if (p.n_tiles == 0) return ACCV_OK;
-    const int groups_x = (p.tiles_x + WPG - 1) / WPG;
-    dim3 grid, block(WPG * 64);
+    const int groups_x = (p.tiles_x + kWavesPerGroup - 1) / kWavesPerGroup;
+    dim3 grid, block(kWavesPerGroup * 64);
     p.grid3d = (planes <= 65535 && p.tiles_y <= 65535) ? 1 : 0;
     if (p.grid3d) {
         grid = dim3((unsigned)groups_x, (unsigned)p.tiles_y, (unsigned)planes);
     } else {
-        const long long groups = (p.n_tiles + WPG - 1) / WPG;
+        const long long groups = (p.n_tiles + kWavesPerGroup - 1) / kWavesPerGroup;
         if (groups > INT_MAX) return accv::fail(ACCV_EINVAL, "draw_heatmap: %lld tiles exceed the grid limit", p.n_tiles);
         grid = dim3((unsigned)groups);
     }
-#define ACCV_LAUNCH_ONE(KERNEL) launch_maybe_timed(KERNEL, grid, block, stream, ev, p)
-#define ACCV_LAUNCH_SM(SMV)                                                                              \
-    do {                                                                                                 \
-        if (clear)                                                                                       \
-            ACCV_LAUNCH_ONE((splat_kernel<PX, R, true, SMV, WPG>));                                      \
-        else                                                                                             \
-            ACCV_LAUNCH_ONE((splat_kernel<PX, R, false, SMV, WPG>));                                     \
-    } while (0)
-    if constexpr (PX == 4) {
-        switch (sm) {
-#ifdef ACCV_TUNE_BUILD
-            case 1: ACCV_LAUNCH_SM(1); break;
-            case 2: ACCV_LAUNCH_SM(2); break;
-#endif
-            case 4: ACCV_LAUNCH_SM(4); break;
-            case 5:  // density-adaptive (in-place launches only; a fused-clear launch asking for it gets plain stores)
-                if (clear) {
-                    sm = 0;
-                    ACCV_LAUNCH_SM(0);
-                } else {
-                    ACCV_LAUNCH_ONE((splat_kernel<PX, R, false, 5, WPG>));
-                }
-                break;
-            default: sm = 0; ACCV_LAUNCH_SM(0); break;
-        }
+    if (PX == 1 || (sm == 5 && clear)) sm = 0;
+    if (sm == 5) {
+        if constexpr (PX == 4) launch_maybe_timed(splat_kernel<PX, R, false, 5>, grid, block, stream, ev, p);
     } else {
-        sm = 0;
-        ACCV_LAUNCH_SM(0);
+        with_variant(clear, sm == 4, [&](auto CL, auto SM) {
+            if constexpr (PX == 4 || SM == 0) launch_maybe_timed(splat_kernel<PX, R, CL, SM>, grid, block, stream, ev, p);
+        });
     }
-#undef ACCV_LAUNCH_SM
-#undef ACCV_LAUNCH_ONE
     note_dispatch("splat_kernel", PX, R, clear, sm, grid, block);
     return accv::check_launch("draw_heatmap splat kernel");
 }
@@ -1677,61 +1657,44 @@ int dispatch_splat(SplatParams p, long long planes, bool clear, unsigned flags, 
     // build the same A/B on four boxes of the slow class puts R = 8 ahead by 1.1-2.8 % on the headline batch and 6 % on
     // small-object batches (profiles/r02_h1_flags_ab_*.log), and in-place launches always preferred it.  R = 16 stays
     // available as a hint (ACCV_HM_TILE_ROWS_16).  Store policy: plain stores for fused-clear launches; in-place launches
-    // decide per plane inside the kernel (SM = 5); ACCV_HM_WRITE_THROUGH / ACCV_HM_PLAIN_STORES override.  No knob table,
-    // mutex or string look-up on this path.
+    // decide per plane inside the kernel (SM = 5); ACCV_HM_WRITE_THROUGH / ACCV_HM_PLAIN_STORES override.
     const bool plane_fits_rsrc = (size_t)p.H * p.W * sizeof(float) < ((size_t)1 << 31);
-    int nt = accv::tune_get("hm_nt", -1);
-    if (nt < 0) {
-        if (flags & ACCV_HM_WRITE_THROUGH)
-            nt = 4;
-        else if (flags & ACCV_HM_PLAIN_STORES)
-            nt = 0;
-        else
-            nt = clear ? 0 : 5;   // in-place: per-plane choice by object density (see the store loop of splat_body)
-    }
+    int nt;
+    if (flags & ACCV_HM_WRITE_THROUGH)
+        nt = 4;
+    else if (flags & ACCV_HM_PLAIN_STORES)
+        nt = 0;
+    else
+        nt = clear ? 0 : 5;   // in-place: per-plane choice by object density (see the store loop of splat_body)
     if (nt >= 2 && !plane_fits_rsrc) nt = 0;
     p.dense_area = 0.75f * (float)p.H * (float)p.W;
-    int rows = accv::tune_get("hm_rows", -1);
-    if (rows < 0) {
-        if (flags & ACCV_HM_TILE_ROWS_16)
-            rows = 16;
-        else if (flags & ACCV_HM_TILE_ROWS_8)
-            rows = 8;
-        else
-            rows = 8;
-        // ... with one exception (round 3): a fused-clear launch whose 128 x 16 tiles are MORE than the chip holds at once (24
-        // one-wave workgroups per CU) while its 128 x 32 tiles all fit (16 per CU) runs as a single round of resident tiles
-        // instead of one full round plus a short second one — the 8-frame shards of the strong-scaling split (8160 tiles on
-        // 256 CUs): 18.1 / 13.8 -> 17.3 / 13.2 us slowest / fastest shard (profiles/r03_small_launch_tile_rows.log); 16 frames
-        // and more, which need several rounds either way, keep R = 8 (+0.5..1.5 % with 128 x 32 there)
-        if (!(flags & (ACCV_HM_TILE_ROWS_8 | ACCV_HM_TILE_ROWS_16)) && clear && vec4 && !small_hint) {
-            const long long cus = compute_units();
-            const long long tx = (p.W + 127) / 128;
-            const long long tiles8 = planes * tx * ((p.H + 15) / 16), tiles16 = planes * tx * ((p.H + 31) / 32);
-            if (cus > 0 && tiles8 > 24 * cus && tiles16 <= 16 * cus) rows = 16;
-        }
+    int rows = (flags & ACCV_HM_TILE_ROWS_16) ? 16 : 8;
+    // ... with one exception (round 3): a fused-clear launch whose 128 x 16 tiles are MORE than the chip holds at once (24
+    // one-wave workgroups per CU) while its 128 x 32 tiles all fit (16 per CU) runs as a single round of resident tiles
+    // instead of one full round plus a short second one — the 8-frame shards of the strong-scaling split (8160 tiles on
+    // 256 CUs): 18.1 / 13.8 -> 17.3 / 13.2 us slowest / fastest shard (profiles/r03_small_launch_tile_rows.log); 16 frames
+    // and more, which need several rounds either way, keep R = 8 (+0.5..1.5 % with 128 x 32 there)
+    if (!(flags & (ACCV_HM_TILE_ROWS_8 | ACCV_HM_TILE_ROWS_16)) && clear && vec4 && !small_hint) {
+        const long long cus = compute_units();
+        const long long tx = (p.W + 127) / 128;
+        const long long tiles8 = planes * tx * ((p.H + 15) / 16), tiles16 = planes * tx * ((p.H + 31) / 32);
+        if (cus > 0 && tiles8 > 24 * cus && tiles16 <= 16 * cus) rows = 16;
     }
     if (!p.labels) p.labels = p.radii;  // branch-free candidate loads: always a readable array (ignored when cls < 0)
     if (!vec4) return launch_splat<1, 8>(p, planes, clear, 0, stream, ev);
-    const int small = accv::tune_get("hm_small", -1);   // point-like objects: the caller's ACCV_HM_SMALL_RADII hint
-    // the small-splat kernel has no per-plane density choice: point-like objects are the sparse case, where write-through
-    // costs up to 27 %, so the adaptive default (5) means PLAIN stores there; only an explicit
-    // ACCV_HM_WRITE_THROUGH selects SM = 4
-    if (small > 0 || (small < 0 && small_hint)) return launch_splat_small(p, planes, clear, nt == 5 ? 0 : nt, stream, ev);
+    // point-like objects (the caller's ACCV_HM_SMALL_RADII hint): the small-splat kernel has no per-plane density choice.
+    // Point-like objects are the sparse case, where write-through costs up to 27 %, so the adaptive default (5)
+    // means PLAIN stores there; only an explicit ACCV_HM_WRITE_THROUGH selects SM = 4
+    if (small_hint) return launch_splat_small(p, planes, clear, nt == 4, stream, ev);
     if (rows == 16) return launch_splat<4, 16>(p, planes, clear, nt, stream, ev);
-#ifdef ACCV_TUNE_BUILD
-    if (accv::tune_get("hm_wpg", kWavesPerGroup) == 4) return launch_splat<4, 8, 4>(p, planes, clear, nt, stream, ev);
-#endif
     return launch_splat<4, 8>(p, planes, clear, nt, stream, ev);
 }
 
-int check_common(const void* hm, int h, int w, float factor, const char* who)
+int check_common(int h, int w, const char* who)
 {
     if (h < 0 || w < 0) return accv::fail(ACCV_EINVAL, "%s: negative heatmap extent %dx%d", who, h, w);
     if (h > (1 << 29) || w > (1 << 29))
         return accv::fail(ACCV_EINVAL, "%s: heatmap extent %dx%d exceeds 2^29 per dimension", who, h, w);
-    (void)hm;
-    (void)factor;
     return ACCV_OK;
 }
 
@@ -1755,6 +1718,51 @@ inline void coarse_scales_first(MultiParams& mp)
 inline void seal_tile_prefix(MultiParams& mp)
 {
     for (int i = mp.n_scales + 1; i <= kMaxScales; ++i) mp.tile_begin[i] = mp.tile_begin[mp.n_scales];
+}
+
+// store mode of the multi-scale launches: plain stores unless the caller asks for write-through (SM = 4).  (dispatch_splat has
+// the single-scale policy, with its per-plane choice for in-place launches.)
+inline int multiscale_store_mode(unsigned flags) { return (flags & ACCV_HM_WRITE_THROUGH) ? 4 : 0; }
+
+// end of the map-rule message of the box and point entry points (the polyline entry point's message has none)
+constexpr const char* kPerScaleNote = " (use the per-scale calls otherwise)";
+// The per-scale set-up of the multi-scale entry points: checks each map (`who` names the entry point, `map_note` ends the
+// message of the map rule), fills mp.scale[0..used) from `proto` plus the scale's map, extent, stride and 128 x tile_h tile
+// counts (maps of zero extent are skipped), and builds the tile prefix.  Returns the tile total, or a negative status.
+long long setup_scales(MultiParams& mp, const SplatParams& proto, float* const* heatmaps, const int* heights, const int* widths,
+                       const float* strides, int num_scales, int batch, int tile_h, unsigned flags, const char* who,
+                       const char* map_note)
+{
+    long long tiles = 0;
+    int used = 0;
+    for (int i = 0; i < num_scales; ++i) {
+        if (int rc = check_common(heights[i], widths[i], who)) return rc;
+        if (!(strides[i] > 0.0f)) return accv::fail(ACCV_EINVAL, "%s: stride %d is not positive", who, i);
+        if (heights[i] == 0 || widths[i] == 0) continue;
+        if (!heatmaps[i]) return accv::fail(ACCV_EINVAL, "%s: heatmap %d is null", who, i);
+        if (widths[i] % 4 != 0 || (reinterpret_cast<uintptr_t>(heatmaps[i]) & 15u) ||
+            (size_t)heights[i] * widths[i] * sizeof(float) >= ((size_t)1 << 31))
+            return accv::fail(ACCV_EINVAL, "%s: map %d needs a width that is a multiple of 4, a 16-byte aligned base and planes "
+                                           "below 2 GiB%s", who, i, map_note);
+        SplatParams& p = mp.scale[used];
+        p = proto;
+        p.hm = heatmaps[i];
+        p.H = heights[i];
+        p.W = widths[i];
+        p.stride = strides[i];
+        p.tiles_x = (p.W + 127) / 128;
+        p.tiles_y = (p.H + tile_h - 1) / tile_h;
+        p.n_tiles = (long long)batch * p.tiles_x * p.tiles_y;
+        p.grid3d = 0;
+        mp.tile_begin[used] = tiles;
+        tiles += p.n_tiles;
+        ++used;
+    }
+    mp.n_scales = used;
+    mp.tile_begin[used] = tiles;
+    if (!(flags & ACCV_HM_CALLER_SCALE_ORDER)) coarse_scales_first(mp);
+    seal_tile_prefix(mp);
+    return tiles;
 }
 
 }  // namespace
@@ -1782,7 +1790,7 @@ int accv_draw_heatmap_flat_f32(float* heatmaps, int num_planes, int height, int 
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const LaunchEvents ev = take_launch_events();   // consumed by this call whether or not it launches
-    if (int rc = check_common(heatmaps, height, width, diameter_to_sigma_factor, "draw_heatmap")) return rc;
+    if (int rc = check_common(height, width, "draw_heatmap")) return rc;
     if (num_planes < 0 || num_objects < 0) return accv::fail(ACCV_EINVAL, "draw_heatmap: negative count");
     if (num_objects > (1 << 30)) return accv::fail(ACCV_EINVAL, "draw_heatmap: more than 2^30 objects");
     const bool clear = (flags & ACCV_HM_CLEAR) != 0;
@@ -1838,7 +1846,7 @@ int accv_draw_heatmap_batched_f32(float* heatmap, int batch, int num_classes, in
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const LaunchEvents ev = take_launch_events();   // consumed by this call whether or not it launches
-    if (int rc = check_common(heatmap, height, width, diameter_to_sigma_factor, "draw_heatmap_batched")) return rc;
+    if (int rc = check_common(height, width, "draw_heatmap_batched")) return rc;
     if (batch < 0 || max_num_targets < 0 || num_classes < 0)
         return accv::fail(ACCV_EINVAL, "draw_heatmap_batched: negative count");
     if (max_num_targets > (1 << 30))
@@ -1956,80 +1964,38 @@ int draw_multiscale_impl(float* const* heatmaps, const int* heights, const int* 
     const bool clear = (flags & ACCV_HM_CLEAR) != 0;
     if (max_num_targets == 0 && !clear) return sampler_only();
 
+    SplatParams proto{};
+    proto.counts = counts;
+    proto.n_max = max_num_targets;
+    proto.factor = diameter_to_sigma_factor;
+    proto.k = k_scale;
+    proto.counts_i64 = (flags & ACCV_HM_COUNTS_I64) ? 1 : 0;
+    proto.centers_f = centers_xy;
+    proto.boxes_f = boxes_xyxy;
     MultiParams mp{};
-    long long tiles = 0;
-    int used = 0;
-    for (int i = 0; i < num_scales; ++i) {
-        if (int rc = check_common(heatmaps[i], heights[i], widths[i], diameter_to_sigma_factor, "draw_heatmap_multiscale"))
-            return rc;
-        if (!(strides[i] > 0.0f)) return accv::fail(ACCV_EINVAL, "draw_heatmap_multiscale: stride %d is not positive", i);
-        if (heights[i] == 0 || widths[i] == 0) continue;
-        if (!heatmaps[i]) return accv::fail(ACCV_EINVAL, "draw_heatmap_multiscale: heatmap %d is null", i);
-        if (widths[i] % 4 != 0 || (reinterpret_cast<uintptr_t>(heatmaps[i]) & 15u) ||
-            (size_t)heights[i] * widths[i] * sizeof(float) >= ((size_t)1 << 31))
-            return accv::fail(ACCV_EINVAL, "draw_heatmap_multiscale: map %d needs a width that is a multiple of 4, a 16-byte "
-                                           "aligned base and planes below 2 GiB (use the per-scale calls otherwise)", i);
-        SplatParams& p = mp.scale[used];
-        p.hm = heatmaps[i];
-        p.counts = counts;
-        p.H = heights[i];
-        p.W = widths[i];
-        p.n_max = max_num_targets;
-        p.factor = diameter_to_sigma_factor;
-        p.k = k_scale;
-        p.counts_i64 = (flags & ACCV_HM_COUNTS_I64) ? 1 : 0;
-        p.centers_f = centers_xy;
-        p.boxes_f = boxes_xyxy;
-        p.stride = strides[i];
-        p.tiles_x = (p.W + 127) / 128;
-        p.tiles_y = (p.H + 2 * ACCV_BOX_TILE_R - 1) / (2 * ACCV_BOX_TILE_R);
-        p.n_tiles = (long long)batch * p.tiles_x * p.tiles_y;
-        p.grid3d = 0;
-        mp.tile_begin[used] = tiles;
-        tiles += p.n_tiles;
-        ++used;
-    }
-    mp.n_scales = used;
-    mp.tile_begin[used] = tiles;
-    if (used == 0 || tiles == 0) return sampler_only();
+    const long long tiles = setup_scales(mp, proto, heatmaps, heights, widths, strides, num_scales, batch, 2 * kBoxTileR, flags,
+                                         "draw_heatmap_multiscale", kPerScaleNote);
+    if (tiles < 0) return (int)tiles;
+    if (tiles == 0) return sampler_only();
     if (tiles + (sampler ? sampler->n_polylines : 0) > INT_MAX)
         return accv::fail(ACCV_EINVAL, "draw_heatmap_multiscale: %lld tiles exceed the grid limit", tiles);
-    if (!(flags & ACCV_HM_CALLER_SCALE_ORDER)) coarse_scales_first(mp);
-    seal_tile_prefix(mp);
-    int nt = accv::tune_get("hm_nt", -1);
-    if (nt < 0) nt = (flags & ACCV_HM_WRITE_THROUGH) ? 4 : 0;   // same store policy as the single-scale path
+    const int sm = multiscale_store_mode(flags);
     if (sampler) {
         TargetsParams tp{};
         tp.mp = mp;
         tp.sp = *sampler;
         const dim3 grid((unsigned)(tiles + sampler->n_polylines)), block(64);
-        if (clear) {
-            if (nt >= 2)
-                hipLaunchKernelGGL((splat_multi_sampler_kernel<true, 4>), grid, block, 0, stream, tp);
-            else
-                hipLaunchKernelGGL((splat_multi_sampler_kernel<true, 0>), grid, block, 0, stream, tp);
-        } else {
-            if (nt >= 2)
-                hipLaunchKernelGGL((splat_multi_sampler_kernel<false, 4>), grid, block, 0, stream, tp);
-            else
-                hipLaunchKernelGGL((splat_multi_sampler_kernel<false, 0>), grid, block, 0, stream, tp);
-        }
-        note_dispatch("splat_multi_sampler_kernel", 4, 8, clear, nt >= 2 ? 4 : 0, grid, block);
+        with_variant(clear, sm == 4, [&](auto CL, auto SM) {
+            hipLaunchKernelGGL((splat_multi_sampler_kernel<CL, SM>), grid, block, 0, stream, tp);
+        });
+        note_dispatch("splat_multi_sampler_kernel", 4, 8, clear, sm, grid, block);
         return accv::check_launch("draw_heatmap multi-scale splat + sampler kernel");
     }
     const dim3 grid((unsigned)tiles), block(64);
-    if (clear) {
-        if (nt >= 2)
-            hipLaunchKernelGGL((splat_multi_kernel<true, 4>), grid, block, 0, stream, mp);
-        else
-            hipLaunchKernelGGL((splat_multi_kernel<true, 0>), grid, block, 0, stream, mp);
-    } else {
-        if (nt >= 2)
-            hipLaunchKernelGGL((splat_multi_kernel<false, 4>), grid, block, 0, stream, mp);
-        else
-            hipLaunchKernelGGL((splat_multi_kernel<false, 0>), grid, block, 0, stream, mp);
-    }
-    note_dispatch("splat_multi_kernel", 4, 8, clear, nt >= 2 ? 4 : 0, grid, block);
+    with_variant(clear, sm == 4, [&](auto CL, auto SM) {
+        hipLaunchKernelGGL((splat_multi_kernel<CL, SM>), grid, block, 0, stream, mp);
+    });
+    note_dispatch("splat_multi_kernel", 4, 8, clear, sm, grid, block);
     return accv::check_launch("draw_heatmap multi-scale splat kernel");
 }
 }  // namespace
@@ -2067,55 +2033,27 @@ int accv_draw_points_multiscale_f32(float* const* heatmaps, const int* heights, 
                           workspace_bytes);
     const int n_groups = (num_points + 63) / 64;
 
+    SplatParams proto{};
+    proto.counts = counts;
+    proto.n_max = num_points;
+    proto.factor = diameter_to_sigma_factor;
+    proto.k = k_scale;
+    proto.counts_i64 = (flags & ACCV_HM_COUNTS_I64) ? 1 : 0;
+    proto.centers_f = points_xy;
+    proto.boxes_f = static_cast<const float*>(workspace);
+    proto.radius = radius;
+    proto.n_groups = n_groups;
     MultiParams mp{};
-    long long tiles = 0;
-    int used = 0;
-    for (int i = 0; i < num_scales; ++i) {
-        if (int rc = check_common(heatmaps[i], heights[i], widths[i], diameter_to_sigma_factor, "draw_points_multiscale"))
-            return rc;
-        if (!(strides[i] > 0.0f)) return accv::fail(ACCV_EINVAL, "draw_points_multiscale: stride %d is not positive", i);
-        if (heights[i] == 0 || widths[i] == 0) continue;
-        if (!heatmaps[i]) return accv::fail(ACCV_EINVAL, "draw_points_multiscale: heatmap %d is null", i);
-        if (widths[i] % 4 != 0 || (reinterpret_cast<uintptr_t>(heatmaps[i]) & 15u) ||
-            (size_t)heights[i] * widths[i] * sizeof(float) >= ((size_t)1 << 31))
-            return accv::fail(ACCV_EINVAL, "draw_points_multiscale: map %d needs a width that is a multiple of 4, a 16-byte "
-                                           "aligned base and planes below 2 GiB (use the per-scale calls otherwise)", i);
-        SplatParams& p = mp.scale[used];
-        p.hm = heatmaps[i];
-        p.counts = counts;
-        p.H = heights[i];
-        p.W = widths[i];
-        p.n_max = num_points;
-        p.factor = diameter_to_sigma_factor;
-        p.k = k_scale;
-        p.counts_i64 = (flags & ACCV_HM_COUNTS_I64) ? 1 : 0;
-        p.centers_f = points_xy;
-        p.boxes_f = static_cast<const float*>(workspace);
-        p.stride = strides[i];
-        p.radius = radius;
-        p.n_groups = n_groups;
-        p.tiles_x = (p.W + 127) / 128;
-        p.tiles_y = (p.H + 15) / 16;
-        p.n_tiles = (long long)batch * p.tiles_x * p.tiles_y;
-        p.grid3d = 0;
-        mp.tile_begin[used] = tiles;
-        tiles += p.n_tiles;
-        ++used;
-    }
-    mp.n_scales = used;
-    mp.tile_begin[used] = tiles;
-    if (used == 0 || tiles == 0) return ACCV_OK;
+    const long long tiles = setup_scales(mp, proto, heatmaps, heights, widths, strides, num_scales, batch, kSmallTH, flags,
+                                         "draw_points_multiscale", kPerScaleNote);
+    if (tiles <= 0) return (int)tiles;   // an error, or no map to draw
     if (tiles > INT_MAX) return accv::fail(ACCV_EINVAL, "draw_points_multiscale: %lld tiles exceed the grid limit", tiles);
-    if (!(flags & ACCV_HM_CALLER_SCALE_ORDER)) coarse_scales_first(mp);
-    seal_tile_prefix(mp);
     const long long total_groups = (long long)batch * n_groups;
     if (total_groups > INT_MAX) return accv::fail(ACCV_EINVAL, "draw_points_multiscale: too many point groups");
     if (total_groups > 0 && !(flags & ACCV_HM_GROUP_BOXES_GIVEN))
         hipLaunchKernelGGL(group_boxes_kernel, dim3((unsigned)total_groups), dim3(64), 0, stream,
                            reinterpret_cast<const float2*>(points_xy), num_points, n_groups, total_groups,
                            static_cast<float4*>(workspace));
-    int nt = accv::tune_get("hm_nt", -1);
-    if (nt < 0) nt = (flags & ACCV_HM_WRITE_THROUGH) ? 4 : 0;
     // a tile of a coarse scale is crossed by several lanes and has many sample groups to walk: share it among four waves
     // when some scale averages >= 24 samples per tile (config 3: 7.5 / 30 / 113 at strides 4 / 8 / 16); fine scales alone
     // keep one wave per tile (mostly empty tiles would only pay the barriers: 21.7 -> 23.8 us at stride 4)
@@ -2124,52 +2062,18 @@ int accv_draw_points_multiscale_f32(float* const* heatmaps, const int* heights, 
     // (9 KB of LDS, 17-20 tiles resident per CU instead of 8) is what the fine scale wants: config 3 (strides 4 / 8 / 16)
     // 32.9 -> 28.7 us, its empty-tile floor 21 -> 15 us (profiles/r03_lane_splat_modes_sweep4_tile_height.log)
     long long coarse_tiles = 0;
-    for (int i = 0; i < used; ++i)
+    for (int i = 0; i < mp.n_scales; ++i)
         if ((double)batch * num_points >= 24.0 * (double)mp.scale[i].n_tiles) coarse_tiles += mp.scale[i].n_tiles;
-    bool heavy = 2 * coarse_tiles >= tiles;
-    if (const int nw = accv::tune_get("pts_nw", -1); nw > 0) heavy = nw == 4;   // A/B build only
-#ifdef ACCV_TUNE_BUILD
-    if (accv::tune_get("pts_th", 16) == 8) {   // experiment: 128 x 8 tiles, one wave each (5 KB of LDS: 32 tiles per CU)
-        long long t8 = 0;
-        for (int i = 0; i < used; ++i) {
-            SplatParams& p = mp.scale[i];
-            p.tiles_y = (p.H + 7) / 8;
-            p.n_tiles = (long long)batch * p.tiles_x * p.tiles_y;
-            mp.tile_begin[i] = t8;
-            t8 += p.n_tiles;
-        }
-        mp.tile_begin[used] = t8;
-        seal_tile_prefix(mp);
-        const dim3 grid8((unsigned)t8);
-        if (clear)
-            hipLaunchKernelGGL((splat_points_multi_kernel<true, 0, 1, 8>), grid8, dim3(64), 0, stream, mp);
-        else
-            hipLaunchKernelGGL((splat_points_multi_kernel<false, 0, 1, 8>), grid8, dim3(64), 0, stream, mp);
-        note_dispatch("splat_points_multi_kernel(TH=8)", 4, 4, clear, 0, grid8, dim3(64));
-        return accv::check_launch("draw_heatmap multi-scale point splat kernel");
-    }
-#endif
+    const bool heavy = 2 * coarse_tiles >= tiles;
+    const int sm = multiscale_store_mode(flags);
     const dim3 grid((unsigned)tiles), block(heavy ? 256 : 64);
-#define ACCV_LAUNCH_POINTS(CL, SMV)                                                                       \
-    do {                                                                                                  \
-        if (heavy)                                                                                        \
-            hipLaunchKernelGGL((splat_points_multi_kernel<CL, SMV, 4>), grid, block, 0, stream, mp);      \
-        else                                                                                              \
-            hipLaunchKernelGGL((splat_points_multi_kernel<CL, SMV, 1>), grid, block, 0, stream, mp);      \
-    } while (0)
-    if (clear) {
-        if (nt >= 2)
-            ACCV_LAUNCH_POINTS(true, 4);
+    with_variant(clear, sm == 4, [&](auto CL, auto SM) {
+        if (heavy)
+            hipLaunchKernelGGL((splat_points_multi_kernel<CL, SM, 4>), grid, block, 0, stream, mp);
         else
-            ACCV_LAUNCH_POINTS(true, 0);
-    } else {
-        if (nt >= 2)
-            ACCV_LAUNCH_POINTS(false, 4);
-        else
-            ACCV_LAUNCH_POINTS(false, 0);
-    }
-#undef ACCV_LAUNCH_POINTS
-    note_dispatch("splat_points_multi_kernel", 4, 8, clear, nt >= 2 ? 4 : 0, grid, block);
+            hipLaunchKernelGGL((splat_points_multi_kernel<CL, SM, 1>), grid, block, 0, stream, mp);
+    });
+    note_dispatch("splat_points_multi_kernel", 4, 8, clear, sm, grid, block);
     return accv::check_launch("draw_heatmap multi-scale point splat kernel");
 }
 
@@ -2210,7 +2114,6 @@ int accv_draw_polylines_fused_applicable(const int* heights, const int* widths, 
                                          int points, int num_samples)
 {
     if (!heights || !widths || num_scales < 1 || num_scales > kMaxScales) return 0;
-    if (accv::tune_get("lane_fused", 1) == 0) return 0;   // A/B build only
     return fused_lane_shape(heights, widths, num_scales, batch, lanes, points, num_samples).ok ? 1 : 0;
 }
 
@@ -2238,46 +2141,18 @@ int accv_draw_polylines_multiscale_f32(float* const* heatmaps, const int* height
         return accv::fail(ACCV_EINVAL, "draw_polylines_multiscale: polylines need 8-byte alignment");
     const bool clear = (flags & ACCV_HM_CLEAR) != 0;
 
+    SplatParams proto{};
+    proto.counts = lane_counts;
+    proto.n_max = lanes;
+    proto.factor = diameter_to_sigma_factor;
+    proto.k = k_scale;
+    proto.counts_i64 = (flags & ACCV_HM_COUNTS_I64) ? 1 : 0;
+    proto.radius = radius;
     FusedLaneParams fp{};
-    MultiParams& mp = fp.mp;
-    long long tiles = 0;
-    int used = 0;
-    for (int i = 0; i < num_scales; ++i) {
-        if (int rc = check_common(heatmaps[i], heights[i], widths[i], diameter_to_sigma_factor, "draw_polylines_multiscale"))
-            return rc;
-        if (!(strides[i] > 0.0f)) return accv::fail(ACCV_EINVAL, "draw_polylines_multiscale: stride %d is not positive", i);
-        if (heights[i] == 0 || widths[i] == 0) continue;
-        if (!heatmaps[i]) return accv::fail(ACCV_EINVAL, "draw_polylines_multiscale: heatmap %d is null", i);
-        if (widths[i] % 4 != 0 || (reinterpret_cast<uintptr_t>(heatmaps[i]) & 15u) ||
-            (size_t)heights[i] * widths[i] * sizeof(float) >= ((size_t)1 << 31))
-            return accv::fail(ACCV_EINVAL, "draw_polylines_multiscale: map %d needs a width that is a multiple of 4, a 16-byte "
-                                           "aligned base and planes below 2 GiB", i);
-        SplatParams& p = mp.scale[used];
-        p.hm = heatmaps[i];
-        p.counts = lane_counts;
-        p.H = heights[i];
-        p.W = widths[i];
-        p.n_max = lanes;
-        p.factor = diameter_to_sigma_factor;
-        p.k = k_scale;
-        p.counts_i64 = (flags & ACCV_HM_COUNTS_I64) ? 1 : 0;
-        p.stride = strides[i];
-        p.radius = radius;
-        p.n_groups = 0;
-        p.tiles_x = (p.W + 127) / 128;
-        p.tiles_y = (p.H + 15) / 16;
-        p.n_tiles = (long long)batch * p.tiles_x * p.tiles_y;
-        p.grid3d = 0;
-        mp.tile_begin[used] = tiles;
-        tiles += p.n_tiles;
-        ++used;
-    }
-    mp.n_scales = used;
-    mp.tile_begin[used] = tiles;
-    if (used == 0 || tiles == 0) return ACCV_OK;
+    const long long tiles = setup_scales(fp.mp, proto, heatmaps, heights, widths, strides, num_scales, batch, kSmallTH, flags,
+                                         "draw_polylines_multiscale", "");
+    if (tiles <= 0) return (int)tiles;   // an error, or no map to draw
     if (tiles > INT_MAX) return accv::fail(ACCV_EINVAL, "draw_polylines_multiscale: %lld tiles exceed the grid limit", tiles);
-    if (!(flags & ACCV_HM_CALLER_SCALE_ORDER)) coarse_scales_first(mp);
-    seal_tile_prefix(mp);
     fp.lp.points = reinterpret_cast<const float2*>(polylines_xy);
     fp.lp.point_counts = point_counts;
     fp.lp.L = lanes;
@@ -2285,21 +2160,12 @@ int accv_draw_polylines_multiscale_f32(float* const* heatmaps, const int* height
     fp.lp.S = num_samples;
     fp.lp.p2_shift = shape.p2_shift;
     fp.lp.counts_i64 = (flags & ACCV_HM_POINT_COUNTS_I64) ? 1 : 0;
-    int nt = accv::tune_get("hm_nt", -1);
-    if (nt < 0) nt = (flags & ACCV_HM_WRITE_THROUGH) ? 4 : 0;
+    const int sm = multiscale_store_mode(flags);
     const dim3 grid((unsigned)tiles), block(64);
-    if (clear) {
-        if (nt >= 2)
-            hipLaunchKernelGGL((lane_raster_multi_kernel<true, 4>), grid, block, 0, stream, fp);
-        else
-            hipLaunchKernelGGL((lane_raster_multi_kernel<true, 0>), grid, block, 0, stream, fp);
-    } else {
-        if (nt >= 2)
-            hipLaunchKernelGGL((lane_raster_multi_kernel<false, 4>), grid, block, 0, stream, fp);
-        else
-            hipLaunchKernelGGL((lane_raster_multi_kernel<false, 0>), grid, block, 0, stream, fp);
-    }
-    note_dispatch("lane_raster_multi_kernel", 4, 8, clear, nt >= 2 ? 4 : 0, grid, block);
+    with_variant(clear, sm == 4, [&](auto CL, auto SM) {
+        hipLaunchKernelGGL((lane_raster_multi_kernel<CL, SM>), grid, block, 0, stream, fp);
+    });
+    note_dispatch("lane_raster_multi_kernel", 4, 8, clear, sm, grid, block);
     return accv::check_launch("draw_heatmap fused lane raster kernel");
 }
 

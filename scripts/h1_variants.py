@@ -2,7 +2,6 @@
 """In-process A/B of splat-kernel variants on the C1 workload (interleaved rounds, one process —
 cdna_hip_programming.md §5.4 rule 24). Prints ms/batch, frames/s and algorithmic GB/s per variant."""
 import argparse
-import itertools
 import os
 import sys
 from types import SimpleNamespace
@@ -24,10 +23,6 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warm", type=int, default=300, help="untimed launches of a variant before its timed ones")
-    ap.add_argument("--knobs", default="",
-                    help="knobs of the A/B build (make -C accv-lab_amd/csrc tune; run with "
-                         "ACCV_HIP_LIB=accv-lab_amd/accvlab/_amd_native/libaccv_hip_tune.so): hm_wpg=1|4, hm_rows=8|16, "
-                         "hm_nt=0|1|2|4, e.g. 'hm_wpg=1,4;hm_nt=0,4'.  Empty: the shipped dispatch only")
     ap.add_argument("--empty", action="store_true", help="no objects: isolates the store pattern")
     ap.add_argument("--nmin", type=int, default=1, help="minimum objects per frame (128 = densest case)")
     ap.add_argument("--alt-lib", default=None,
@@ -45,14 +40,6 @@ def main():
     r = SimpleNamespace(tensor=rpad.to(dev), sample_sizes=sizes.to(dev))
     hm = torch.zeros((B, H, W), device=dev)
     nbytes = B * H * W * 4
-    knobs = []
-    for part in [p for p in args.knobs.split(";") if p]:
-        k, vals = part.split("=")
-        knobs.append([(k, int(v)) for v in vals.split(",")])
-    variants = list(itertools.product(*knobs)) if knobs else [()]
-    has_knobs = hasattr(nat.ctypes_lib(), "accv_tune_set")
-    if knobs and not has_knobs:
-        raise SystemExit("--knobs needs the A/B build: make -C accv-lab_amd/csrc tune && ACCV_HIP_LIB=.../libaccv_hip_tune.so")
     lib = nat.lib()
     stream = torch.cuda.current_stream().cuda_stream
 
@@ -90,16 +77,10 @@ def main():
         res.setdefault(("fill",), []).append(t)
         t = timed(lambda: hm.zero_())
         res.setdefault(("torch.zero_",), []).append(t)
-        for var in variants:
-            for k, v in var:
-                nat.tune_set(k, v)
-            for mode in ("clear", "inplace"):
-                t = timed(lambda: draw_heatmap_batched(hm, c, r, 6.0, 1.0, clear=(mode == "clear")))
-                res.setdefault(var + (mode,), []).append(t)
-        if alt is not None:  # both builds through the bare C-ABI, default knobs
-            for k, v in (("hm_wpg", 1), ("hm_rows", -1), ("hm_nt", -1)):
-                if has_knobs:
-                    nat.tune_set(k, v)
+        for mode in ("clear", "inplace"):
+            t = timed(lambda: draw_heatmap_batched(hm, c, r, 6.0, 1.0, clear=(mode == "clear")))
+            res.setdefault((mode,), []).append(t)
+        if alt is not None:  # both builds through the bare C-ABI
             for mode in ("clear", "inplace"):
                 for name, handle in (("shipped", lib), ("alt", alt)):
                     t = timed(lambda: draw_with(handle, mode == "clear"))

@@ -114,6 +114,73 @@ def test_lane_raster_shape_rule_and_rider_argument_checks_without_gpu():
     assert rider(9, 64, ctypes.c_void_p(68)) == -1 and b"alignment" in lib.accv_last_error()
 
 
+_MAP_RULE = "needs a width that is a multiple of 4, a 16-byte aligned base and planes below 2 GiB"
+_FUSED_SHAPE = ("draw_polylines_multiscale: shape outside the fused kernel (1..64 points per polyline, lanes x points rounded up "
+                "to a power of two <= 64, samples <= (points - 1) x that power of two / 2, fine scales in the majority: "
+                "accv_draw_polylines_fused_applicable); use accv_polyline_sample_boxes + accv_draw_points_multiscale_f32")
+# (heatmaps, heights, widths, strides, num_scales, batch) -> (status, accv_last_error() text or None); {who} is the entry
+# point's name, {rule} the map rule with the entry point's suffix.  Nothing here gets as far as a launch.
+_MULTISCALE_CASES = {
+    "no_scales": ((64,), (256,), (1024,), (4.0,), 0, 2, -1, "{who}: 1..4 scales supported, got 0"),
+    "five_scales": ((64,) * 5, (256,) * 5, (1024,) * 5, (4.0,) * 5, 5, 2, -1, "{who}: 1..4 scales supported, got 5"),
+    "five_scales_empty_batch": ((64,) * 5, (256,) * 5, (1024,) * 5, (4.0,) * 5, 5, 0, -1, "{who}: 1..4 scales supported, got 5"),
+    "null_arrays": (None, (256,), (1024,), (4.0,), 1, 2, -1, "{who}: null array"),
+    "zero_stride": ((64, 64), (256, 256), (1024, 1024), (4.0, 0.0), 2, 2, -1, "{who}: stride 1 is not positive"),
+    "negative_stride": ((64, 64), (256, 256), (1024, 1024), (-4.0, 8.0), 2, 2, -1, "{who}: stride 0 is not positive"),
+    "nan_stride": ((64, 64), (256, 256), (1024, 1024), (4.0, float("nan")), 2, 2, -1, "{who}: stride 1 is not positive"),
+    "null_map": ((64, None), (256, 256), (1024, 1024), (4.0, 8.0), 2, 2, -1, "{who}: heatmap 1 is null"),
+    "null_map_of_zero_extent_skipped": ((None, None), (0, 16), (1024, 1024), (4.0, 8.0), 2, 2, -1, "{who}: heatmap 1 is null"),
+    "width_not_multiple_of_4": ((64, 64), (256, 256), (1024, 1022), (4.0, 8.0), 2, 2, -1, "{who}: map 1 {rule}"),
+    "misaligned_map": ((64, 72), (256, 256), (1024, 1024), (4.0, 8.0), 2, 2, -1, "{who}: map 1 {rule}"),
+    "plane_of_2_gib": ((64, 64), (1 << 14, 256), (1 << 15, 1024), (4.0, 8.0), 2, 2, -1, "{who}: map 0 {rule}"),
+    "negative_extent": ((64, 64), (16, -1), (1024, 1024), (4.0, 8.0), 2, 2, -1, "{who}: negative heatmap extent -1x1024"),
+    "extent_above_2_29": ((64,), (1 << 30,), (1024,), (4.0,), 1, 2, -1,
+                          "{who}: heatmap extent 1073741824x1024 exceeds 2^29 per dimension"),
+    "empty_batch": ((64,), (256,), (1024,), (4.0,), 1, 0, 0, None),
+    "empty_batch_bad_maps": ((None, 72), (256, -1), (1022, 1024), (0.0, 8.0), 2, 0, 0, None),
+    "every_map_zero_extent": ((None, None), (0, 256), (1024, 0), (4.0, 8.0), 2, 2, 0, None),
+}
+# entries that differ from the table for one entry point: the polyline path takes every zero-extent map through its
+# shape rule
+_MULTISCALE_OVERRIDES = {
+    ("polylines", "every_map_zero_extent"): (-1, _FUSED_SHAPE),
+}
+
+
+@pytest.mark.parametrize("entry", ["boxes", "boxes_sample", "points", "polylines"])
+@pytest.mark.parametrize("case", sorted(_MULTISCALE_CASES))
+def test_multiscale_map_validation_without_gpu(entry, case):
+    """host-side validation of the multi-scale entry points, pinned with status and full error text: scale count, per-map
+    stride / extent / null / width / alignment / size checks in the order they fire, empty batches and all-empty maps.
+    The other arguments pass every earlier check (the box path with the sampler rider is given no polylines)."""
+    from accvlab import _amd_native as nat
+
+    lib = nat.ctypes_lib()
+    hm, hs, ws, st, n, batch, want, text = _MULTISCALE_CASES[case]
+    want, text = _MULTISCALE_OVERRIDES.get((entry, case), (want, text))
+    arr = lambda ctype, v: None if v is None else (ctype * len(v))(*v)
+    maps, hs, ws, st = arr(ctypes.c_void_p, hm), arr(ctypes.c_int, hs), arr(ctypes.c_int, ws), arr(ctypes.c_float, st)
+    d = ctypes.c_void_p(64)
+    clear = 1   # fused clear: a call without objects still has maps to write
+    if entry == "boxes":
+        who, suffix = "draw_heatmap_multiscale", " (use the per-scale calls otherwise)"
+        status = lib.accv_draw_heatmap_multiscale_f32(maps, hs, ws, st, n, batch, None, None, d, 0, 6.0, 1.0, clear, None)
+    elif entry == "boxes_sample":
+        who, suffix = "draw_heatmap_multiscale", " (use the per-scale calls otherwise)"
+        status = lib.accv_draw_heatmap_multiscale_sample_f32(maps, hs, ws, st, n, batch, None, None, d, 0, 6.0, 1.0, clear,
+                                                             None, 0, 9, None, 64, None, None, None)
+    elif entry == "points":
+        who, suffix = "draw_points_multiscale", " (use the per-scale calls otherwise)"
+        status = lib.accv_draw_points_multiscale_f32(maps, hs, ws, st, n, batch, None, d, 0, 2, 6.0, 1.0, clear, d, 16, None)
+    else:
+        who, suffix = "draw_polylines_multiscale", ""
+        status = lib.accv_draw_polylines_multiscale_f32(maps, hs, ws, st, n, batch, d, 1, 24, None, d, 32, 2, 6.0, 1.0, clear,
+                                                        None)
+    assert status == want, lib.accv_last_error()
+    if text is not None:
+        assert lib.accv_last_error().decode() == text.format(who=who, rule=_MAP_RULE + suffix)
+
+
 @pytest.mark.parametrize("value", [4, 1, 0])
 def test_null_pointer_sweep_is_rejected_or_empty(value):
     """every int-returning entry point called with NULL for every pointer and `value` for every integer: the call must come
