@@ -48,10 +48,11 @@ def _hint_flags(clear: bool, small_radii: bool, write_through: bool, tile_rows) 
         (_nat.HM_TILE_ROWS_16 if tile_rows == 16 else _nat.HM_TILE_ROWS_8 if tile_rows == 8 else 0) | _FORCED_FLAGS
 
 
-def _quick_geometry(maps, batch: int, device):
+def _one_launch_maps(maps, batch: int, device):
     """``(ptrs, heights, widths)`` as ctypes arrays when every map is a contiguous float32 ``[batch, H, W]`` CUDA tensor on
-    ``device`` that the one-launch multi-scale kernels take (width a multiple of 4, 16-byte aligned, planes below 2 GiB), else
-    ``None`` — one pass over the maps for callers that hand the arrays on (draw_targets_multiscale)."""
+    ``device`` that the one-launch multi-scale kernels take (1 to 4 maps, width a multiple of 4, 16-byte aligned, planes below
+    2 GiB), else ``None``.  The only place that decides this; maps it declines go through :func:`_check_maps`, and the valid
+    ones then take the per-scale operators."""
     k = len(maps)
     if not 1 <= k <= 4:
         return None
@@ -70,6 +71,18 @@ def _quick_geometry(maps, batch: int, device):
         hs.append(shape[1])
         ws.append(shape[2])
     return (ctypes.c_void_p * k)(*ptrs), (ctypes.c_int * k)(*hs), (ctypes.c_int * k)(*ws)
+
+
+def _check_maps(maps, batch: int, device, owner: str) -> None:
+    """``RuntimeError`` for maps that even the per-scale operators reject: not a contiguous float32 ``[batch, H, W]`` CUDA
+    tensor on ``device`` (the device of the ``owner``: centers or polylines)."""
+    for hm in maps:
+        _check_input(hm, "heatmap")
+        _check_dtype(hm, torch.float32, "heatmap")
+        if not (hm.dim() == 3 and hm.size(0) == batch):
+            raise RuntimeError("every heatmap must be of shape [batch_size, height, width]")
+        if not (hm.device == device):
+            raise RuntimeError(f"every heatmap must be on the {owner}' device ({device})")
 
 
 def _require(cond: bool, msg: str) -> None:
@@ -99,7 +112,7 @@ def _same_device(ref: torch.Tensor, *others) -> None:
 
 _FLAT_DIRECT_MAX_OBJECTS = 2048
 _FLAT_DIRECT_MAX_ROUNDS = 200_000     # tiles x cull rounds of 64 objects: ~8 M wave instructions, a few microseconds of the chip
-_count_cache = {}
+_constants: dict = {}
 
 
 def _flat_direct(planes: int, height: int, width: int, n: int) -> bool:
@@ -109,19 +122,19 @@ def _flat_direct(planes: int, height: int, width: int, n: int) -> bool:
     return tiles * ((n + 63) // 64) <= _FLAT_DIRECT_MAX_ROUNDS
 
 
-def _one_count(n: int, device) -> torch.Tensor:
-    """int32 [1] = n on `device`, shared by later calls on any stream (created once: its stream is drained before it is
-    published; nothing is cached while a stream is being captured)."""
-    key = (n, device)
-    t = _count_cache.get(key)
+def _device_constant(key, make) -> torch.Tensor:
+    """Device constants (object counts, sample fractions) shared by every later call — on ANY stream.  The tensor is created
+    on the stream that is current at the first call, so that stream is drained once before the tensor is published; while a
+    stream is being captured into a graph nothing is cached (no synchronisation allowed there)."""
+    t = _constants.get(key)
     if t is None:
-        t = torch.full((1,), n, dtype=torch.int32, device=device)
+        t = make()
         if torch.cuda.is_current_stream_capturing():
             return t
-        torch.cuda.current_stream(device).synchronize()
-        if len(_count_cache) > 256:
-            _count_cache.clear()
-        _count_cache[key] = t
+        torch.cuda.current_stream(t.device).synchronize()
+        if len(_constants) > 256:
+            _constants.clear()
+        _constants[key] = t
     return t
 
 
@@ -186,7 +199,8 @@ def draw_heatmap(
         # entry point): every tile tests all N objects instead of its plane's share, which costs less than the binning
         # launch while N is small.  Same values (max is order independent).
         with _nat.device_guard(heatmaps.device):
-            count = _one_count(n, heatmaps.device)
+            dev = heatmaps.device
+            count = _device_constant(("count", n, dev), lambda: torch.full((1,), n, dtype=torch.int32, device=dev))
             status = lib.accv_draw_heatmap_batched_f32(
                 heatmaps.data_ptr(), 1, planes, height, width, centers.data_ptr(), radii.data_ptr(), count.data_ptr(),
                 heatmap_idxes.data_ptr(), n, float(diameter_to_sigma_factor), float(k_scale),
@@ -351,7 +365,7 @@ def get_centers_and_radii(centers, bboxes, out_size_factor: float):
 
 
 def draw_heatmap_multiscale(heatmaps, centers, bboxes, out_size_factors, diameter_to_sigma_factor: float = 6.0,
-                            k_scale: float = 1.0, *, clear: bool = False, _sampler_job=None, _geometry=None) -> None:
+                            k_scale: float = 1.0, *, clear: bool = False) -> None:
     """(extension) Rasterise one batch of objects at several strides.  Equivalent to, for every scale ``s``::
 
         c, r = get_centers_and_radii(centers, bboxes, out_size_factors[s])
@@ -370,6 +384,21 @@ def draw_heatmap_multiscale(heatmaps, centers, bboxes, out_size_factors, diamete
     strides = [float(f) for f in out_size_factors]
     if not (len(heatmaps) == len(strides) and len(heatmaps) >= 1):
         raise RuntimeError("heatmaps and out_size_factors must have the same, non-zero length")
+    objects = _box_objects(centers, bboxes)
+    batch, dev = objects[0].size(0), objects[0].device
+    geometry = _one_launch_maps(heatmaps, batch, dev)
+    if geometry is None:   # odd widths / more than four scales: the per-scale operators
+        _check_maps(heatmaps, batch, dev, "centers")
+        for hm, f in zip(heatmaps, strides):
+            ci, ri = get_centers_and_radii(centers, bboxes, f)
+            draw_heatmap_batched(hm, ci, ri, diameter_to_sigma_factor, k_scale, clear=clear)
+        return
+    _launch_box_maps(geometry, strides, objects, diameter_to_sigma_factor, k_scale, clear)
+
+
+def _box_objects(centers, bboxes):
+    """``(centers, bboxes, counts)`` tensors of :func:`draw_heatmap_multiscale`'s objects, checked: contiguous CUDA float32
+    ``[B, Nmax, 2]`` / ``[B, Nmax, 4]`` and int32 / int64 counts ``[B]`` (other dtypes are widened), all on one device."""
     c_t = centers.tensor
     b_t = bboxes.tensor if hasattr(bboxes, "tensor") else bboxes
     counts = centers.sample_sizes
@@ -384,48 +413,32 @@ def draw_heatmap_multiscale(heatmaps, centers, bboxes, out_size_factors, diamete
         raise RuntimeError("bboxes must be of shape [batch_size, num_targets, 4]")
     _check_dtype(c_t, torch.float32, "centers")
     _check_dtype(b_t, torch.float32, "bboxes")
-    batch, n_max = c_t.shape[:2]
-    if not (counts.dim() == 1 and counts.size(0) == batch):
+    if not (counts.dim() == 1 and counts.size(0) == c_t.size(0)):
         raise RuntimeError("nums_targets must be of shape [batch_size]")
-    fusable = len(heatmaps) <= 4
-    if _geometry is None:
-        _geometry = _quick_geometry(heatmaps, batch, c_t.device)    # one pass when all is well; else the checks below say why
-    if _geometry is not None:
-        _same_device(c_t, ("bboxes", b_t), ("nums_targets", counts))     # (the maps are on the centres' device)
-    for hm in (heatmaps if _geometry is None else ()):     # (_geometry given: draw_targets_multiscale has checked the maps already)
-        _check_input(hm, "heatmap")
-        _check_dtype(hm, torch.float32, "heatmap")
-        if not (hm.dim() == 3 and hm.size(0) == batch):
-            raise RuntimeError("every heatmap must be of shape [batch_size, height, width]")
-        _same_device(hm, ("centers", c_t), ("bboxes", b_t), ("nums_targets", counts))
-        fusable = fusable and hm.size(2) % 4 == 0 and hm.data_ptr() % 16 == 0 and hm.size(1) * hm.size(2) * 4 < (1 << 31)
-    if not fusable:   # odd widths / more than four scales: the per-scale operators
-        for hm, f in zip(heatmaps, strides):
-            ci, ri = get_centers_and_radii(centers, bboxes, f)
-            draw_heatmap_batched(hm, ci, ri, diameter_to_sigma_factor, k_scale, clear=clear)
-        if _sampler_job is not None:
-            _sampler_job.run_separately()
-        return
-    n = len(heatmaps)
-    if _geometry is None:
-        ptrs = (ctypes.c_void_p * n)(*[hm.data_ptr() for hm in heatmaps])
-        hs = (ctypes.c_int * n)(*[hm.size(1) for hm in heatmaps])
-        ws = (ctypes.c_int * n)(*[hm.size(2) for hm in heatmaps])
-    else:
-        ptrs, hs, ws = _geometry
+    _same_device(c_t, ("bboxes", b_t), ("nums_targets", counts))
+    return c_t, b_t, counts
+
+
+def _launch_box_maps(geometry, strides, objects, diameter_to_sigma_factor, k_scale, clear, job=None) -> None:
+    """ONE launch of the multi-scale box-map kernel: ``geometry`` from :func:`_one_launch_maps` for the objects' batch and
+    device, ``objects`` from :func:`_box_objects`.  With a sampler ``job`` (lanes._SamplerJob, draw_targets_multiscale) the
+    polyline sampler rides in the same launch."""
+    ptrs, hs, ws = geometry
+    c_t, b_t, counts = objects
+    batch, n_max = c_t.shape[:2]
+    n = len(strides)
     st = (ctypes.c_float * n)(*strides)
     flags = (_nat.HM_CLEAR if clear else 0) | (_nat.HM_COUNTS_I64 if counts.dtype == torch.int64 else 0) | _FORCED_FLAGS
-    dev = heatmaps[0].device
+    dev = c_t.device
     with _nat.device_guard(dev):
-        if _sampler_job is None:
+        if job is None:
             status = _nat.lib().accv_draw_heatmap_multiscale_f32(
                 ptrs, hs, ws, st, n, batch, c_t.data_ptr(), b_t.data_ptr(), counts.data_ptr(), n_max,
                 float(diameter_to_sigma_factor), float(k_scale), flags, _nat.stream_ptr(dev))
-        else:   # (draw_targets_multiscale) the polyline sampler rides in the same launch
-            j = _sampler_job
+        else:
             status = _nat.lib().accv_draw_heatmap_multiscale_sample_f32(
                 ptrs, hs, ws, st, n, batch, c_t.data_ptr(), b_t.data_ptr(), counts.data_ptr(), n_max,
-                float(diameter_to_sigma_factor), float(k_scale), flags | j.flags, j.points.data_ptr(), j.num_polylines, j.num_points,
-                j.counts.data_ptr() if j.counts is not None else None, j.num_samples, j.samples.data_ptr(), j.work.data_ptr(),
-                _nat.stream_ptr(dev))
+                float(diameter_to_sigma_factor), float(k_scale), flags | job.flags, job.points.data_ptr(), job.num_polylines,
+                job.num_points, job.counts.data_ptr() if job.counts is not None else None, job.num_samples,
+                job.samples.data_ptr(), job.work.data_ptr(), _nat.stream_ptr(dev))
     _nat.check(status, "draw_heatmap_multiscale")

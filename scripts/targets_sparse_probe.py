@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """draw_targets_multiscale on configs[3]'s maps with SPARSE lane sets (1 / 2 polylines of 24 points per frame): lane maps through
-the sampler riding in the box-map launch + point splat, or through the one-launch lane raster (lane_raster_multi_kernel)?"""
+the sampler riding in the box-map launch + point splat (draw_targets_multiscale), or box maps alone and then the one-launch lane
+raster (lane_raster_multi_kernel: draw_heatmap_multiscale + draw_polylines_multiscale)?"""
 import json
 import os
 import sys
@@ -11,7 +12,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "accv-lab_amd")]
 import torch  # noqa: E402
 
 from accvlab.batching_helpers import combine_data  # noqa: E402
-from accvlab.draw_heatmap import draw_targets_multiscale, lanes as lanes_mod  # noqa: E402
+from accvlab.draw_heatmap import draw_heatmap_multiscale, draw_polylines_multiscale, draw_targets_multiscale  # noqa: E402
 
 
 def gpu_us(fn, n=300, warm=100):
@@ -49,12 +50,18 @@ def main():
     ys = SH * (1 - 0.9 * t_).expand(B, 8, P)
     for nl in (1, 2):
         lanes = torch.stack([xs[:, :nl], ys[:, :nl]], -1).contiguous().to(dev)
+
+        def rider():
+            draw_targets_multiscale(maps, crb, brb, strides, lane_maps, lanes, 256, 2, clear=True)
+
+        def one_launch_lanes():
+            draw_heatmap_multiscale(maps, crb, brb, strides, 6.0, 1.0, clear=True)
+            draw_polylines_multiscale(lane_maps, lanes, 256, 2, strides, clear=True)
+
         best = {True: 1e9, False: 1e9}
         for _ in range(3):
-            for rider in (True, False):
-                lanes_mod.TARGETS_PREFER_RIDER = rider
-                best[rider] = min(best[rider], gpu_us(lambda: draw_targets_multiscale(maps, crb, brb, strides, lane_maps, lanes, 256, 2, clear=True)))
-        lanes_mod.TARGETS_PREFER_RIDER = True
+            for use_rider, fn in ((True, rider), (False, one_launch_lanes)):
+                best[use_rider] = min(best[use_rider], gpu_us(fn))
         print(json.dumps({"polylines_per_frame": nl, "rider_plus_point_splat_us": round(best[True], 2),
                           "one_launch_lane_raster_us": round(best[False], 2)}), flush=True)
 

@@ -14,7 +14,8 @@ import torch  # noqa: E402
 
 from accvlab import _amd_native as nat  # noqa: E402
 from accvlab.batching_helpers import combine_data  # noqa: E402
-from accvlab.draw_heatmap import draw_heatmap_multiscale, draw_polylines_multiscale, draw_targets_multiscale, sample_lanes  # noqa: E402
+from accvlab.draw_heatmap import draw_heatmap_multiscale, draw_targets_multiscale, sample_lanes  # noqa: E402
+from accvlab.draw_heatmap import lanes as lanes_mod, ops  # noqa: E402
 
 
 def main():
@@ -54,7 +55,9 @@ def main():
             draw_heatmap_multiscale(maps, crb, brb, strides, 6.0, 1.0, clear=True)
             done = torch.cuda.Event()
             done.record(side)
-        draw_polylines_multiscale(lane_maps, lanes, S, 2, strides, clear=True, _presampled=(samples, work))
+        # the point splat of draw_polylines_multiscale on these samples and the group boxes the sampler wrote
+        sizes = lanes_mod._lane_sizes(None, B, L, S, dev)
+        lanes_mod._splat_points(ops._one_launch_maps(lane_maps, B, dev), strides, samples, sizes, 2, 6.0, 1.0, True, work, True)
         main_s.wait_event(done)
 
     def wall_us(fn, n=500, warm=200):

@@ -226,3 +226,25 @@ def test_single_scale_call_takes_the_point_splat_and_equals_the_three_launch_for
             assert kernel in nat.last_dispatch(), (stride, radius, width, nat.last_dispatch())
             via_targets(ref, pts_d, 96, radius, stride, 6.0, 0.7, num_points=npts_d, num_lanes=nlanes_d, clear=clear)
             assert torch.equal(got, ref), (stride, radius, width, clear)
+
+
+@pytest.mark.parametrize("l,fused", [(2, True), (8, False)])
+def test_multiscale_lane_raster_rejects_host_num_lanes(l, fused):
+    """a CPU num_lanes raises RuntimeError before any launch, on the one-launch (fused) and on the two-launch path"""
+    import ctypes
+
+    from accvlab import _amd_native as nat
+    from accvlab.draw_heatmap import draw_polylines_multiscale
+
+    dev = torch.device("cuda", 0)
+    b, p, q, sw, sh = 2, 24, 256, 3072.0, 1728.0
+    strides = (4.0, 8.0, 16.0)
+    shapes = [(b, int(sh / s), int(sw / s)) for s in strides]
+    hs, ws = (ctypes.c_int * 3)(*[s_[1] for s_ in shapes]), (ctypes.c_int * 3)(*[s_[2] for s_ in shapes])
+    assert bool(nat.lib().accv_draw_polylines_fused_applicable(hs, ws, 3, b, l, p, q)) == fused
+    pts, _, _ = _lanes(b, l, p, sw, sh, seed=l, ragged=False)
+    maps = [torch.full(s_, 0.5, device=dev) for s_ in shapes]
+    with pytest.raises(RuntimeError):
+        draw_polylines_multiscale(maps, torch.from_numpy(pts).to(dev), q, 2, strides, num_lanes=torch.full((b,), l), clear=True)
+    torch.cuda.synchronize()
+    assert all(bool((m == 0.5).all()) for m in maps)

@@ -21,7 +21,7 @@ def _same_samples(a, b):
     return bool((na == nb).all()) and torch.equal(torch.where(na, zero, a).view(torch.int32), torch.where(nb, zero, b).view(torch.int32))
 
 
-def _objects(b, n_max, sw, sh, seed):
+def _objects(b, n_max, sw, sh, seed, dev=DEV):
     from accvlab.batching_helpers import RaggedBatch
 
     g = torch.Generator().manual_seed(seed)
@@ -29,7 +29,7 @@ def _objects(b, n_max, sw, sh, seed):
     half = torch.rand(b, n_max, 2, generator=g) * 60 + 2
     boxes = torch.cat([c - half, c + half], -1)
     n = torch.randint(0, n_max + 1, (b,), generator=g)
-    return RaggedBatch(c.to(DEV), sample_sizes=n.to(DEV)), RaggedBatch(boxes.to(DEV), sample_sizes=n.to(DEV))
+    return RaggedBatch(c.to(dev), sample_sizes=n.to(dev)), RaggedBatch(boxes.to(dev), sample_sizes=n.to(dev))
 
 
 def _polylines(b, l, p, sw, sh, seed, ragged):
@@ -72,7 +72,7 @@ def test_targets_equal_the_two_operators(ragged, clear, l, p, q, radius):
 
 @pytest.mark.parametrize("counts_dtype", [None, torch.int32, torch.int64])
 @pytest.mark.parametrize("l,p,q", [(8, 24, 256), (1, 64, 64), (7, 1, 64), (5, 2, 128), (3, 37, 320)])
-def test_rider_writes_what_the_sampler_launch_writes(l, p, q, counts_dtype):
+def test_rider_launch_writes_what_the_sampler_launch_writes(l, p, q, counts_dtype):
     """samples and group boxes of the wave-level sampler == accv_polyline_sample_boxes, bit for bit"""
     from accvlab import _amd_native as nat
     from accvlab.draw_heatmap import lanes, ops, sample_lanes
@@ -90,7 +90,7 @@ def test_rider_writes_what_the_sampler_launch_writes(l, p, q, counts_dtype):
     work = torch.zeros(nat.lib().accv_draw_points_workspace_bytes(b, l * q), dtype=torch.uint8, device=DEV)
     job = lanes._SamplerJob(pts, npts, q, work)
     maps = [torch.zeros(b, 128, 256, device=DEV)]
-    ops.draw_heatmap_multiscale(maps, centers, boxes, (8.0,), clear=True, _sampler_job=job)
+    ops._launch_box_maps(ops._one_launch_maps(maps, b, DEV), (8.0,), ops._box_objects(centers, boxes), 6.0, 1.0, True, job)
     assert "splat_multi_sampler_kernel" in nat.last_dispatch()
     got_boxes = work[: groups * 16].view(torch.float32).view(groups, 4).clone()
     ref_boxes = torch.zeros(groups, 4, device=DEV)
@@ -105,7 +105,7 @@ def test_rider_writes_what_the_sampler_launch_writes(l, p, q, counts_dtype):
     assert torch.equal(maps[0], plain[0])
 
 
-def test_rider_alone_and_argument_checks():
+def test_rider_launch_alone_and_argument_checks():
     from accvlab import _amd_native as nat
     from accvlab.batching_helpers import RaggedBatch
     from accvlab.draw_heatmap import lanes, ops, sample_lanes
@@ -118,15 +118,21 @@ def test_rider_alone_and_argument_checks():
     empty_c = RaggedBatch(torch.zeros(b, 0, 2, device=DEV), sample_sizes=torch.zeros(b, dtype=torch.int64, device=DEV))
     empty_b = RaggedBatch(torch.zeros(b, 0, 4, device=DEV), sample_sizes=torch.zeros(b, dtype=torch.int64, device=DEV))
     hm = [torch.full((b, 64, 128), 0.5, device=DEV)]
-    ops.draw_heatmap_multiscale(hm, empty_c, empty_b, (4.0,), clear=False, _sampler_job=job)
+    ops._launch_box_maps(ops._one_launch_maps(hm, b, DEV), (4.0,), ops._box_objects(empty_c, empty_b), 6.0, 1.0, False, job)
     assert "splat_multi_sampler_kernel" in nat.last_dispatch() and "grid(6,1,1)" in nat.last_dispatch()
     assert (hm[0] == 0.5).all()
     assert _same_samples(job.samples, sample_lanes(pts, q))
-    # odd map width: the box maps fall back to the per-scale operators and the job runs as the stand-alone sampler
+    # odd box-map width: the box maps take the per-scale operators, so draw_targets_multiscale takes the two calls and the lane
+    # maps get the stand-alone sampler's samples
+    from accvlab.draw_heatmap import draw_heatmap_multiscale, draw_polylines_multiscale, draw_targets_multiscale
+
     centers, boxes = _objects(b, 5, 500.0, 300.0, seed=2)
-    job2 = lanes._SamplerJob(pts, None, q, work)
-    ops.draw_heatmap_multiscale([torch.zeros(b, 75, 125, device=DEV)], centers, boxes, (4.0,), clear=True, _sampler_job=job2)
-    assert _same_samples(job2.samples, sample_lanes(pts, q))
+    box_a, box_b = torch.zeros(b, 75, 125, device=DEV), torch.zeros(b, 75, 125, device=DEV)
+    lane_a, lane_b = torch.zeros(b, 76, 128, device=DEV), torch.zeros(b, 76, 128, device=DEV)
+    draw_targets_multiscale([box_a], centers, boxes, (4.0,), [lane_a], pts, q, 2, clear=True)
+    draw_heatmap_multiscale([box_b], centers, boxes, (4.0,), clear=True)
+    draw_polylines_multiscale([lane_b], pts, q, 2, (4.0,), clear=True)
+    assert torch.equal(box_a, box_b) and torch.equal(lane_a, lane_b) and bool((lane_a > 0).any())
     # C entry point: shapes the wave-level sampler does not take
     lib = nat.lib()
     ptrs = (ctypes.c_void_p * 1)(hm[0].data_ptr())
@@ -167,3 +173,36 @@ def test_targets_replay_in_a_graph():
     torch.cuda.synchronize()
     for a, r in zip(box_g + lane_g, box_r + lane_r):
         assert torch.equal(a, r)
+
+
+def _mismatch_case(centers_frames=3, centers_dev=DEV, num_points=None, num_lanes=None):
+    """draw_targets_multiscale on maps and polylines of 3 frames that would take the rider: RuntimeError, and no launch (the
+    maps, filled with 0.5, stay as they are although clear=True)"""
+    from accvlab.draw_heatmap import draw_targets_multiscale
+
+    b, sw, sh = 3, 1024.0, 512.0
+    strides = (4.0, 8.0)
+    centers, boxes = _objects(centers_frames, 10, sw, sh, seed=8, dev=centers_dev)
+    pts, _, _ = _polylines(b, 4, 20, sw, sh, seed=9, ragged=False)
+    maps = [torch.full((b, int(sh / s), int(sw / s)), 0.5, device=DEV) for s in strides + strides]
+    with pytest.raises(RuntimeError):
+        draw_targets_multiscale(maps[:2], centers, boxes, strides, maps[2:], pts, 128, 2, num_points=num_points,
+                                num_lanes=num_lanes, clear=True)
+    torch.cuda.synchronize()
+    assert all(bool((m == 0.5).all()) for m in maps)
+
+
+@pytest.mark.parametrize("frames", [4, 2])
+def test_targets_reject_centres_of_another_batch(frames):
+    _mismatch_case(centers_frames=frames)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_targets_reject_centres_on_another_device():
+    _mismatch_case(centers_dev=torch.device("cuda", 1))
+
+
+@pytest.mark.parametrize("arg", ["num_lanes", "num_points"])
+def test_targets_reject_host_counts(arg):
+    counts = {"num_lanes": torch.full((3,), 2, dtype=torch.int32), "num_points": torch.full((3, 4), 20, dtype=torch.int32)}
+    _mismatch_case(**{arg: counts[arg]})
