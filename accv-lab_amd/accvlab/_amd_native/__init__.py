@@ -32,6 +32,9 @@ HM_POINT_COUNTS_I64 = 512
 MP_IDX_I64 = 1
 MP_COUNTS_I64 = 2
 MP_LABELS_I64 = 4
+FL_AVG_NUM_POS = 0
+FL_AVG_VALUE = 1
+FL_AVG_DEVICE = 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -79,6 +82,10 @@ SIGNATURES = {
     "accv_matched_pair_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _f, _f, _u, _vp, _vp]),
     "accv_matched_pair_reduce_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _f, _f, _u,
                                           _vp, _vp, _vp, _vp]),
+    # Gaussian focal loss on a heat-map target
+    "accv_gaussian_focal_loss_workspace_bytes": (_sz, [_ll]),
+    "accv_gaussian_focal_loss": (_i, [_vp, _vp, _ll, _i, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "accv_gaussian_focal_loss_bwd": (_i, [_vp, _vp, _ll, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),

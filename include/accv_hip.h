@@ -287,6 +287,33 @@ int accv_matched_pair_reduce_bwd(const void* a, const void* b, const void* idx_a
                                  int dtype, float beta, float eps, unsigned flags, void* grad_a_or_null,
                                  void* grad_b_or_null, void* grad_w_or_null, void* stream);
 
+/* Gaussian focal loss on a drawn heat-map target — the GaussianFocalLoss centerness term the draw_heatmap maps are drawn for
+ * (packages/draw_heatmap/docs/intro.rst:7-25), forward and backward in one streaming pass each:
+ *   p = clamp(sigmoid(logits), eps, 1 - eps)   (clamp_eps = 0: no clamp)
+ *   l = pos_weight * [target == 1] * -log(p + 1e-12) * (1 - p)^alpha
+ *     + neg_weight * -log(1 - p + 1e-12) * p^alpha * (1 - target)^gamma
+ *   out_loss = sum(l) / denom,  denom = max(#{target == 1}, 1) (ACCV_FL_AVG_NUM_POS, counted exactly in the same pass),
+ *              avg_factor (ACCV_FL_AVG_VALUE) or *avg_factor_dev (ACCV_FL_AVG_DEVICE, f32 device scalar)
+ * logits [numel] of dtype 0 f32, 1 f16, 2 bf16 (the codes of accv_matched_pair_reduce), target f32 [numel]; arithmetic in
+ * f32, per-block partials in f64 summed in a fixed order by a second one-block launch: no atomics, bitwise reproducible.
+ * out_loss and out_denom are f32 device scalars; the backward reads out_denom.  alpha >= 1, gamma >= 0, 0 <= clamp_eps < 0.5.
+ * workspace: accv_gaussian_focal_loss_workspace_bytes(numel) bytes of device memory, 16-byte aligned.  numel == 0 launches
+ * nothing (and writes nothing). */
+#define ACCV_FL_AVG_NUM_POS 0
+#define ACCV_FL_AVG_VALUE 1
+#define ACCV_FL_AVG_DEVICE 2
+size_t accv_gaussian_focal_loss_workspace_bytes(long long numel);
+int accv_gaussian_focal_loss(const void* logits, const float* target, long long numel, int dtype, float alpha, float gamma,
+                             float pos_weight, float neg_weight, float clamp_eps, int avg_mode, float avg_factor,
+                             const float* avg_factor_dev, float* out_loss, float* out_denom, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* Its backward, element-wise: grad_logits = *grad_out / *denom * dl/dlogits in the logits dtype, written once (no atomics, no
+ * zero-initialisation needed).  The clamp passes gradient only where eps <= sigmoid(x) <= 1 - eps (torch.clamp's inclusive
+ * mask); the rest is torch autograd of the formula above. */
+int accv_gaussian_focal_loss_bwd(const void* logits, const float* target, long long numel, int dtype, float alpha, float gamma,
+                                 float pos_weight, float neg_weight, float clamp_eps, const float* grad_out,
+                                 const float* denom, void* grad_logits, void* stream);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */
