@@ -3,12 +3,17 @@
 
 CUDA tensors run ONE kernel of libaccv_hip.so per call (accv_polyline_sample); CPU tensors use a vectorised torch
 implementation that accumulates in float64 (the reference's CPU path accumulates in at::acc_type, polyline_cpu.cpp).
+
+(extension) When grad mode is on and ``points`` or ``distances`` requires grad, the operators run through autograd
+Functions whose backward is a HIP kernel (accv_polyline_grad; accv_polyline_grad_host for CPU tensors): the exact
+derivative of the branch each query took in the forward.  The forward values are the same bits either way.
 """
 from __future__ import annotations
 
 import functools
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from ... import _amd_native as _nat
 
@@ -150,6 +155,96 @@ def _host(points, distances, p_sizes, d_sizes, relative, want_points, want_lengt
     return out_p, out_l
 
 
+def _count_args(p_sizes, d_sizes):
+    """(p_sizes, d_sizes, counts_i64) with ONE integer width for both, as the C-ABI takes them"""
+    present = [t for t in (p_sizes, d_sizes) if t is not None]
+    if not present:
+        return p_sizes, d_sizes, 0
+    wide = any(t.dtype == torch.int64 for t in present)
+    want = torch.int64 if wide else torch.int32
+    p_sizes = p_sizes.to(want).contiguous() if p_sizes is not None else None
+    d_sizes = d_sizes.to(want).contiguous() if d_sizes is not None else None
+    return p_sizes, d_sizes, 1 if wide else 0
+
+
+@functools.lru_cache(maxsize=256)
+def _grad_workspace_bytes(batch: int, max_points: int, max_distances: int, dims: int, code: int) -> int:
+    return int(_nat.lib().accv_polyline_grad_workspace_bytes(batch, max_points, max_distances, dims, code))
+
+
+def _backward(points, distances, p_sizes, d_sizes, relative, grad_out, grad_lengths, want_points, want_distances):
+    """Gradients w.r.t. points / distances of the samples (incoming ``grad_out``) and / or lengths (``grad_lengths``):
+    one launch of accv_polyline_grad (CUDA; workspace from torch, no host synchronisation) or accv_polyline_grad_host."""
+    b, pmax, dims = points.shape
+    qmax = distances.shape[1] if distances is not None else 0
+    grad_p = torch.empty_like(points, memory_format=torch.contiguous_format) if want_points else None
+    grad_d = torch.empty_like(distances, memory_format=torch.contiguous_format) if want_distances else None
+    if b == 0 or (grad_p is None and grad_d is None):
+        return grad_p, grad_d
+    points = points.contiguous()
+    distances = distances.contiguous() if distances is not None else None
+    grad_out = grad_out.contiguous().to(points.dtype) if grad_out is not None else None
+    grad_lengths = grad_lengths.contiguous().to(points.dtype) if grad_lengths is not None else None
+    p_sizes, d_sizes, c64 = _count_args(p_sizes, d_sizes)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    code = _DTYPE_CODE[points.dtype]
+    args = (ptr(points), ptr(distances), ptr(p_sizes), ptr(d_sizes), ptr(grad_out), ptr(grad_lengths), ptr(grad_p),
+            ptr(grad_d), b, pmax, qmax, dims, code, c64, int(bool(relative)))
+    lib = _nat.lib()
+    if points.is_cuda:
+        with _nat.device_guard(points.device):
+            wb = _grad_workspace_bytes(b, pmax, qmax, dims, code)
+            ws = torch.empty(wb, dtype=torch.uint8, device=points.device) if wb else None
+            _nat.check(lib.accv_polyline_grad(*args, ptr(ws), wb, _nat.stream_ptr(points.device)), "polyline backward")
+    else:
+        _nat.check(lib.accv_polyline_grad_host(*args, 0), "polyline backward (host)")
+    return grad_p, grad_d
+
+
+def _forward(points, distances, p_sizes, d_sizes, relative, want_points):
+    run = _gpu if points.is_cuda else _host
+    res = run(points, distances, p_sizes, d_sizes, relative, want_points, not want_points)
+    return res[0] if want_points else res[1]
+
+
+class _Interpolate(torch.autograd.Function):
+    """samples = interpolate(points, distances) with the HIP backward (sizes: None for the fixed-size form)"""
+
+    @staticmethod
+    def forward(ctx, points, distances, p_sizes, d_sizes, relative):
+        ctx.save_for_backward(points, distances, p_sizes, d_sizes)
+        ctx.relative = relative
+        return _forward(points, distances, p_sizes, d_sizes, relative, True)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        points, distances, p_sizes, d_sizes = ctx.saved_tensors
+        gp, gd = _backward(points, distances, p_sizes, d_sizes, ctx.relative, grad_out, None, ctx.needs_input_grad[0],
+                           ctx.needs_input_grad[1])
+        return gp, gd, None, None, None
+
+
+class _Lengths(torch.autograd.Function):
+    """lengths(points) with the HIP backward"""
+
+    @staticmethod
+    def forward(ctx, points, p_sizes):
+        ctx.save_for_backward(points, p_sizes)
+        return _forward(points, None, p_sizes, None, False, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_lengths):
+        points, p_sizes = ctx.saved_tensors
+        gp, _ = _backward(points, None, p_sizes, None, False, None, grad_lengths, ctx.needs_input_grad[0], False)
+        return gp, None
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
 def _cpu_accum(points, p_sizes):
     """float64 accumulated distances [B, P] with +inf behind the valid points, and total lengths."""
     b, pmax, _ = points.shape
@@ -209,7 +304,12 @@ def _cpu_lengths(points, p_sizes):
 def interpolate(points: torch.Tensor, distances: torch.Tensor, *, relative: bool = False) -> torch.Tensor:
     """Sample every polyline of ``points (batch, num_points, num_dims)`` at ``distances (batch, num_distances)`` measured
     along the polyline from its first point (``relative=True``: as fractions of its total length).  Queries before the
-    start / beyond the end clamp to the first / last point.  Returns ``(batch, num_distances, num_dims)``."""
+    start / beyond the end clamp to the first / last point.  Returns ``(batch, num_distances, num_dims)``.
+
+    Differentiable w.r.t. ``points`` and ``distances`` (first order): each sample passes the exact derivative of the
+    branch it took — inside a segment the interpolation (moving the segment's end points and, through the arc length,
+    every earlier segment; with ``relative`` also the total length), otherwise the copied first / last / lower point.
+    Gradients are accumulated with float atomics and may differ in the last bits from run to run."""
     if isinstance(points, torch.Tensor) and points.is_cuda and isinstance(distances, torch.Tensor):
         native = _native()      # plain CUDA call: checks, allocation and the launch in C++ (declines anything unusual)
         if native is not None:
@@ -228,13 +328,16 @@ def interpolate(points: torch.Tensor, distances: torch.Tensor, *, relative: bool
         raise RuntimeError("points and distances must have the same dtype")
     if not (points.device == distances.device):
         raise RuntimeError("points and distances must be on the same device")
+    if _wants_grad(points, distances):
+        return _Interpolate.apply(points, distances, None, None, bool(relative))
     if points.is_cuda:
         return _gpu(points, distances, None, None, relative, True, False)[0]
     return _host(points, distances, None, None, relative, True, False)[0]
 
 
 def lengths(points: torch.Tensor) -> torch.Tensor:
-    """Total length of every polyline of ``points (batch, num_points, num_dims)`` -> ``(batch,)``."""
+    """Total length of every polyline of ``points (batch, num_points, num_dims)`` -> ``(batch,)``.  Differentiable
+    w.r.t. ``points``; segments shorter than epsilon pass no gradient."""
     if isinstance(points, torch.Tensor) and points.is_cuda:
         native = _native()
         if native is not None:
@@ -244,6 +347,8 @@ def lengths(points: torch.Tensor) -> torch.Tensor:
     _check_points(points)
     if not (points.dim() == 3):
         raise RuntimeError("points must have shape (batch, num_points, num_dims)")
+    if _wants_grad(points):
+        return _Lengths.apply(points, None)
     if points.is_cuda:
         return _gpu(points, None, None, None, False, False, True)[1]
     return _host(points, None, None, None, False, False, True)[1]
@@ -260,7 +365,8 @@ def _check_var(points, sizes, name):
 def interpolate_var_size_batch(points, distances, *, relative: bool = False):
     """Ragged variant: ``points`` / ``distances`` are RaggedBatch-like (``(batch, max_num_points, num_dims)`` and
     ``(batch, max_num_distances)``, one batch dimension, non-uniform dimension 1).  Returns a RaggedBatch with the
-    distances' sample sizes."""
+    distances' sample sizes.  Gradients reach ``points.tensor`` / ``distances.tensor`` through its ``tensor``; padded
+    points and distances get zero gradient, padded samples' gradients are ignored."""
     assert points.num_batch_dims == 1, "points must have exactly one batch dimension"
     assert distances.num_batch_dims == 1, "distances must have exactly one batch dimension"
     assert points.non_uniform_dim == 1, "points.non_uniform_dim must be 1 for shape (batch, max_num_points, num_dims)"
@@ -283,6 +389,8 @@ def interpolate_var_size_batch(points, distances, *, relative: bool = False):
     _check_var(pt, ps, "points.sample_sizes")
     _check_var(dt, ds, "distances.sample_sizes")
     _check_size_values([(ps, pt.size(1), "points.sample_sizes"), (ds, dt.size(1), "distances.sample_sizes")])
+    if _wants_grad(pt, dt):
+        return distances.create_with_sample_sizes_like_self(_Interpolate.apply(pt, dt, ps, ds, bool(relative)))
     if pt.is_cuda:
         res = _gpu(pt, dt, ps, ds, relative, True, False)[0]
     else:
@@ -300,6 +408,8 @@ def lengths_var_size_batch(points) -> torch.Tensor:
         raise RuntimeError("points must have shape (batch, max_num_points, num_dims)")
     _check_var(pt, ps, "points.sample_sizes")
     _check_size_values([(ps, pt.size(1), "points.sample_sizes")])
+    if _wants_grad(pt):
+        return _Lengths.apply(pt, ps)
     if pt.is_cuda:
         return _gpu(pt, None, ps, None, False, False, True)[1]
     return _host(pt, None, ps, None, False, False, True)[1]

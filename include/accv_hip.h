@@ -419,6 +419,28 @@ int accv_polyline_sample_boxes(const void* points, const void* distances, const 
                                int max_distances, int num_dims, int dtype, int counts_i64, int relative, void* scratch,
                                size_t scratch_bytes, void* stream);
 
+/* Backward of accv_polyline_sample (an extension: the reference's polyline operators have no gradient).  grad_out
+ * [batch, max_distances, dims] (gradient of out_points) and grad_lengths [batch] (gradient of out_lengths) are in the points'
+ * dtype, either may be NULL; writes grad_points [batch, max_points, dims] and / or grad_distances [batch, max_distances]
+ * (either may be NULL) whole: zeros behind the counts, padded grad_out entries are not read.  Every query takes the segment
+ * the forward's search took (same arithmetic); its gradient is the exact derivative of that branch: inside a segment of
+ * length >= epsilon the interpolation, else the copied point.  Segments shorter than epsilon pass no length gradient;
+ * polylines with 0 or 1 points give zero gradients.  Accumulation as the forward (f32 for f32 / f16 / bf16, f64 for f64;
+ * the segment-length gradients are scanned in f64), through LDS / global float atomics: results may differ in the last
+ * bits from run to run.  workspace: accv_polyline_grad_workspace_bytes(batch, max_points, max_distances, num_dims, dtype)
+ * bytes of device memory with the same extents (max_distances = 0 when there are no distances).  No host synchronisation. */
+size_t accv_polyline_grad_workspace_bytes(long long batch, int max_points, int max_distances, int num_dims, int dtype);
+int accv_polyline_grad(const void* points, const void* distances, const void* point_counts, const void* dist_counts,
+                       const void* grad_out, const void* grad_lengths, void* grad_points, void* grad_distances,
+                       long long batch, int max_points, int max_distances, int num_dims, int dtype, int counts_i64,
+                       int relative, void* workspace, size_t workspace_bytes, void* stream);
+/* Its counterpart on HOST memory (accv_polyline_sample_host's backward): float32 / float64 only, double accumulation, up to
+ * `threads` host threads (0 = automatic).  No HIP call. */
+int accv_polyline_grad_host(const void* points, const void* distances, const void* point_counts, const void* dist_counts,
+                            const void* grad_out, const void* grad_lengths, void* grad_points, void* grad_distances,
+                            long long batch, int max_points, int max_distances, int num_dims, int dtype, int counts_i64,
+                            int relative, int threads);
+
 /* Streaming fill used by bench.py as the measured write-bandwidth ceiling (not part of the reference API). */
 int accv_fill_f32(float* dst, size_t count, float value, void* stream);
 
