@@ -86,6 +86,9 @@ SIGNATURES = {
     "accv_gaussian_focal_loss_workspace_bytes": (_sz, [_ll]),
     "accv_gaussian_focal_loss": (_i, [_vp, _vp, _ll, _i, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "accv_gaussian_focal_loss_bwd": (_i, [_vp, _vp, _ll, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    # heat-map peak extraction (local-maximum suppression + top-k)
+    "accv_heatmap_peaks_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll, _i]),
+    "accv_heatmap_peaks": (_i, [_vp, _i, _ll, _ll, _ll, _ll, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),

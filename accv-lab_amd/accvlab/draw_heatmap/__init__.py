@@ -7,15 +7,17 @@ class-wise planes).  Both accept one extra keyword, ``clear=False``: with ``clea
 overwritten with max(0, splats) in a single write-only pass (fused zero-fill + draw).
 Extensions next to them: ``get_centers_and_radii`` (bbox -> centre/radius front end) and ``draw_polylines_batched`` /
 ``sample_lane_targets`` (lane raster = polyline sampler + splat), ``draw_heatmap_multiscale`` (all strides of a batch in one
-launch), ``draw_targets_multiscale`` (box maps + lane maps of a step in two launches), and the maps' consumer
-``gaussian_focal_loss`` (the fused GaussianFocalLoss centerness term, forward and backward).
+launch), ``draw_targets_multiscale`` (box maps + lane maps of a step in two launches), the maps' consumer
+``gaussian_focal_loss`` (the fused GaussianFocalLoss centerness term, forward and backward), and their read-back
+``heatmap_peaks`` (local-maximum suppression + top-k in two launches, with a defined tie order).
 """
 from .focal_loss import gaussian_focal_loss
 from .lanes import (draw_polylines_batched, draw_polylines_multiscale, draw_targets_multiscale, sample_lane_targets,
                     sample_lanes)
 from .ops import draw_heatmap, draw_heatmap_batched, draw_heatmap_multiscale, get_centers_and_radii
+from .peaks import HeatmapPeaks, heatmap_peaks
 
 __version__ = "0.1.0"
 __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_and_radii", "draw_polylines_batched",
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
-           "gaussian_focal_loss"]
+           "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks"]

@@ -314,6 +314,24 @@ int accv_gaussian_focal_loss_bwd(const void* logits, const float* target, long l
                                  float pos_weight, float neg_weight, float clamp_eps, const float* grad_out,
                                  const float* denom, void* grad_logits, void* stream);
 
+/* Heat-map peak extraction — mmdet's get_local_maximum + get_topk_from_heatmap (models/utils/gaussian_target.py), the
+ * read-back half of the maps draw_heatmap draws, fused into two launches:
+ *   s = x * (x == max over the kernel x kernel window)   (window clipped at the border: max_pool2d's -inf padding)
+ *   per group the k largest s in descending order, equal scores by ascending flat index in the group
+ *   (= torch.sort(s, descending=True, stable=True)[:k]).  A group is a frame of C*H*W elements (per_class == 0) or one
+ *   (b, c) plane of H*W (per_class != 0); it must hold at least k and fewer than 2^32 - 1 elements.
+ * x [B, C, H, W] contiguous, dtype 0 f32, 1 f16, 2 bf16 (the codes of accv_gaussian_focal_loss); kernel odd in 1..7;
+ * 1 <= k <= 1024.  Outputs [groups, k]: scores in the input dtype (the values of x, suppressed ones +0.0), indices
+ * y * W + x in the plane, classes (the plane's channel), ys, xs — all int64.  No atomics decide the order: results are
+ * bitwise reproducible.  workspace: accv_heatmap_peaks_workspace_bytes(B, C, H, W, k) bytes of device memory, 16-byte
+ * aligned (0 for sizes the call refuses).  Returns ACCV_EINVAL (negative size, unknown dtype, even or out-of-range kernel,
+ * k out of range or above the group size, a group of 2^32 - 1 or more elements, null pointers) or ACCV_EWORKSPACE before
+ * touching the device, ACCV_ELAUNCH if a launch fails; B == 0 launches nothing. */
+size_t accv_heatmap_peaks_workspace_bytes(long long B, long long C, long long H, long long W, int k);
+int accv_heatmap_peaks(const void* x, int dtype, long long B, long long C, long long H, long long W, int kernel, int k,
+                       int per_class, void* scores, long long* indices, long long* classes, long long* ys, long long* xs,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */
