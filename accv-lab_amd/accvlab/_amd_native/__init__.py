@@ -35,6 +35,9 @@ MP_LABELS_I64 = 4
 FL_AVG_NUM_POS = 0
 FL_AVG_VALUE = 1
 FL_AVG_DEVICE = 2
+LSA_MAXIMIZE = 1
+LSA_THREADS_64 = 2
+LSA_THREADS_1024 = 4
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -89,6 +92,10 @@ SIGNATURES = {
     # heat-map peak extraction (local-maximum suppression + top-k)
     "accv_heatmap_peaks_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll, _i]),
     "accv_heatmap_peaks": (_i, [_vp, _i, _ll, _ll, _ll, _ll, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # batched linear sum assignment (Hungarian matching)
+    "accv_linear_assignment_workspace_bytes": (_sz, [_ll, _ll, _ll, _i]),
+    "accv_linear_assignment": (_i, [_vp, _i, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "accv_linear_assignment_host": (_i, [_vp, _i, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _u, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -129,7 +136,7 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 # entry points that BLOCK (wait for a native job, run a long host memcpy): they stay on ctypes, which drops the
 # interpreter lock for the duration of the call — the trampoline keeps it
 _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
-             "accv_polyline_grad_host"}
+             "accv_polyline_grad_host", "accv_linear_assignment_host"}
 
 
 def _fast_entry(fn, res, args):

@@ -33,6 +33,7 @@ from .batched_processing_py import (
 )
 
 from .fused import matched_pair_loss_sum  # (extension) gathers + per-object loss + masked sum in one launch
+from .assignment import batched_linear_sum_assignment  # (extension) per-frame Hungarian matching in one launch
 
 __version__ = "0.1.0"
 
@@ -46,6 +47,7 @@ __all__ = [
     "batched_index_mapping",
     "batched_indexing_access",
     "batched_indexing_write",
+    "batched_linear_sum_assignment",
     "batched_inverse_indexing_access",
     "combine_data",
     "get_compact_from_named_tuple",

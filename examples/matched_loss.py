@@ -59,6 +59,18 @@ def match_batched(gt_boxes: bh.RaggedBatch, gt_labels: bh.RaggedBatch, pred_boxe
     return gt_rb.to_device(dev), pred_rb.to_device(dev)
 
 
+def match_batched_on_device(gt_boxes: bh.RaggedBatch, gt_labels: bh.RaggedBatch, pred_boxes, pred_scores, check=True):
+    """``match_batched`` without the host round trip: the same padded cost matrices, solved per frame on their own device
+    by ``bh.batched_linear_sum_assignment`` (padded gt columns are never read).  ``check=False`` skips the one status read
+    (no host synchronisation; a frame without a complete matching then has no pairs instead of raising)."""
+    num_classes = pred_scores.shape[-1]
+    cost = (1.0 - _iou(pred_boxes.unsqueeze(2), gt_boxes.tensor.unsqueeze(1))) + \
+           (1.0 - torch.einsum("bqc,bgc->bqg", pred_scores, _one_hot(gt_labels.tensor, num_classes)))
+    cost = gt_labels.create_with_sample_sizes_like_self(cost.detach(), non_uniform_dim=2)
+    pred_rb, gt_rb = bh.batched_linear_sum_assignment(cost, check=check)[:2]
+    return gt_rb, pred_rb
+
+
 def loss_batched(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, match_gt, match_pred):
     """Per-frame loss ``[B]`` = class L1 + (1 - IoU) over matched pairs + existence L1 over all predictions."""
     num_q, num_classes = pred_scores.shape[1], pred_scores.shape[2]
@@ -158,4 +170,15 @@ def run_batched(gt_boxes_l, gt_labels_l, gt_weights_l, pred_boxes, pred_scores, 
     gt_weights = bh.combine_data(gt_weights_l, other_with_same_sample_sizes=gt_boxes)
     m_gt, m_pred = match_batched(gt_boxes, gt_labels, pred_boxes, pred_scores)
     fn = loss_batched_fused if fused else loss_batched          # the fused op is GPU-only
+    return fn(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, m_gt, m_pred)
+
+
+def run_batched_on_device(gt_boxes_l, gt_labels_l, gt_weights_l, pred_boxes, pred_scores, pred_exist, fused=False,
+                          check=True):
+    """``run_batched`` with the matching done by ``match_batched_on_device``."""
+    gt_boxes = bh.combine_data(gt_boxes_l)
+    gt_labels = bh.combine_data(gt_labels_l, other_with_same_sample_sizes=gt_boxes)
+    gt_weights = bh.combine_data(gt_weights_l, other_with_same_sample_sizes=gt_boxes)
+    m_gt, m_pred = match_batched_on_device(gt_boxes, gt_labels, pred_boxes, pred_scores, check=check)
+    fn = loss_batched_fused if fused else loss_batched
     return fn(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, m_gt, m_pred)

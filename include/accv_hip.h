@@ -332,6 +332,37 @@ int accv_heatmap_peaks(const void* x, int dtype, long long B, long long C, long 
                        int per_class, void* scores, long long* indices, long long* classes, long long* ys, long long* xs,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ batched assignment
+ * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
+ * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
+ * back).  Per frame b the minimum-cost (ACCV_LSA_MAXIMIZE: maximum-cost) complete matching of the smaller side of the
+ * R_b x C_b block cost[b, :R_b, :C_b], with scipy's semantics: +inf (-inf under maximize) forbids a pair, NaN and -inf
+ * (+inf under maximize) are invalid entries.  Exact: shortest augmenting paths with f64 duals; argmin ties go to an
+ * unassigned column, then the lowest index, so results are bitwise reproducible and equal to the host solver's.
+ * cost: dtype 0 f32, 1 f16, 2 bf16, 3 f64, element (b, r, c) at cost[b * stride_b + r * stride_r + c * stride_c]
+ * (strides in elements; any view).  row_counts / col_counts: device int64 [B] (R_b, C_b), NULL = R / C for every frame,
+ * values clamped to [0, R] / [0, C].  Limits: max(R, C) <= 4096 and min(R, C) <= 1024 of the padded shape.
+ * Outputs, W = min(R, C): row_ind / col_ind int64 [B, W] (the pairs with row_ind ascending, zero from sizes[b] on),
+ * sizes int64 [B] (min(R_b, C_b), 0 for a failed frame), status int32 [B] (0 ok, 1 infeasible, 2 invalid entry).
+ * One workgroup per frame; no host synchronisation.  workspace: accv_linear_assignment_workspace_bytes(B, R, C, dtype)
+ * bytes of device memory, 16-byte aligned (0 for sizes the call refuses).  Returns ACCV_EINVAL (negative or oversized
+ * extent, unknown dtype or flag, null pointers) or ACCV_EWORKSPACE before touching the device, ACCV_ELAUNCH if the
+ * launch fails; B == 0 launches nothing. */
+#define ACCV_LSA_MAXIMIZE 1u
+#define ACCV_LSA_THREADS_64 2u    /* hint: one wave per frame instead of 256 lanes (same results) */
+#define ACCV_LSA_THREADS_1024 4u  /* hint: 1024 lanes per frame (same results) */
+size_t accv_linear_assignment_workspace_bytes(long long B, long long R, long long C, int dtype);
+int accv_linear_assignment(const void* cost, int dtype, long long B, long long R, long long C, long long stride_b,
+                           long long stride_r, long long stride_c, const long long* row_counts,
+                           const long long* col_counts, unsigned flags, long long* row_ind, long long* col_ind,
+                           long long* sizes, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The same solver on the host (same algorithm, tie rule and f64 operation sequence: equal results bit for bit); every
+ * pointer is host memory.  Blocks the calling thread. */
+int accv_linear_assignment_host(const void* cost, int dtype, long long B, long long R, long long C, long long stride_b,
+                                long long stride_r, long long stride_c, const long long* row_counts,
+                                const long long* col_counts, unsigned flags, long long* row_ind, long long* col_ind,
+                                long long* sizes, int* status);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */
