@@ -10,6 +10,7 @@ There is no CPU path in this module (the reference's is CUDA-only too).
 from __future__ import annotations
 
 import functools
+import math
 import struct
 from typing import Optional
 
@@ -115,33 +116,62 @@ def _data_dtype(t, name, allow_bool=False) -> None:
         raise RuntimeError(f"{name}: unsupported data type {t.dtype}")
 
 
-@functools.lru_cache(maxsize=256)
+_FLOAT_BITS = {torch.float32: (torch.int32, 32), torch.float16: (torch.int16, 16), torch.bfloat16: (torch.int16, 16)}
+
+
 def element_bits(value, dtype: torch.dtype) -> int:
     """Byte pattern (as an unsigned integer, little endian) of ``value`` converted to ``dtype`` with the
-    conversion rules of ``static_cast<scalar_t>(double)`` used by the reference."""
+    conversion rules of ``static_cast<scalar_t>(double)`` used by the reference: floating-point types round to nearest
+    even, values beyond the largest finite one become ±inf, NaN stays NaN and -0.0 stays -0.0; integer types truncate
+    toward zero (in-range values only) and bool is ``value != 0``."""
     # normalise to a plain python number first: the cache below must never key on a mutable object (0-dim tensors, numpy
     # scalars) whose value can change under the same identity
     if not isinstance(value, (bool, int, float)):
         value = float(value)
-    return _element_bits(value, dtype)
+    # -0.0 == 0.0 and both hash alike: the sign goes into the cache key, or whichever came first would answer for both
+    negative = isinstance(value, float) and math.copysign(1.0, value) < 0
+    return _element_bits(value, negative, dtype)
 
 
 @functools.lru_cache(maxsize=256)
-def _element_bits(value, dtype: torch.dtype) -> int:
-    if dtype == torch.float32:
-        return struct.unpack("<I", struct.pack("<f", float(value)))[0]
+def _element_bits(value, negative: bool, dtype: torch.dtype) -> int:
     if dtype == torch.float64:
         return struct.unpack("<Q", struct.pack("<d", float(value)))[0]
-    if dtype == torch.float16:
-        return struct.unpack("<H", struct.pack("<e", float(value)))[0]
-    if dtype == torch.bfloat16:
-        return int(torch.tensor(float(value), dtype=torch.bfloat16).view(torch.int16).item()) & 0xFFFF
+    if dtype in _FLOAT_BITS:
+        as_int, bits = _FLOAT_BITS[dtype]
+        x = torch.tensor(float(value), dtype=torch.float64).to(dtype)
+        return int(x.view(as_int).item()) & ((1 << bits) - 1)
     if dtype == torch.bool:
         return 1 if value else 0
     bits = {torch.int8: 8, torch.uint8: 8, torch.int16: 16, torch.int32: 32, torch.int64: 64}.get(dtype)
     if bits is None:
         raise RuntimeError(f"unsupported data type {dtype}")
     return int(value) & ((1 << bits) - 1)
+
+
+_SAME_WIDTH_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def filler_as_int(value, dtype: torch.dtype):
+    """``(int_dtype, v)``: an integer dtype of ``dtype``'s width and the value whose bits are ``element_bits(value,
+    dtype)``.  Filling an integer view with it writes exactly those bits, with no second conversion by torch (which
+    refuses out-of-range fillers instead of rounding them to ±inf)."""
+    size = torch.empty((), dtype=dtype).element_size()
+    bits = element_bits(value, dtype)
+    if size > 1 and bits >> (8 * size - 1):
+        bits -= 1 << (8 * size)
+    return _SAME_WIDTH_INT[size], bits
+
+
+def full_of_filler(shape, value, dtype: torch.dtype, device, requires_grad: bool = False) -> torch.Tensor:
+    """``torch.full(shape, value)`` with the filler converted as ``element_bits`` converts it."""
+    res = torch.empty(shape, dtype=dtype, device=device)
+    if dtype == torch.bool:
+        res.fill_(bool(value))
+    else:
+        as_int, v = filler_as_int(value, dtype)
+        res.view(as_int).fill_(v)
+    return res.requires_grad_(requires_grad) if requires_grad else res
 
 
 def _row_elems(t: torch.Tensor, first_data_dim: int) -> int:
@@ -191,8 +221,7 @@ def forward(input_data: torch.Tensor, input_indices: torch.Tensor, input_nums_in
     _data_dtype(input_data, "input_data")
     res_size = list(input_indices.shape[:nb + 1]) + list(input_data.shape[nb + 1:])
     if input_indices.numel() == 0 or 0 in res_size:
-        return torch.full(res_size, fill_value, dtype=input_data.dtype, device=input_data.device,
-                          requires_grad=input_data.requires_grad)
+        return full_of_filler(res_size, fill_value, input_data.dtype, input_data.device, input_data.requires_grad)
     # the kernel writes every element of the result (gathered rows and the filler): no torch.full pass
     res = torch.empty(res_size, dtype=input_data.dtype, device=input_data.device,
                       requires_grad=input_data.requires_grad)
@@ -254,8 +283,7 @@ def backward_new_tensor(to_insert: torch.Tensor, input_indices: torch.Tensor, in
     _data_dtype(to_insert, "to_insert")
     shape = list(to_insert.shape)
     shape[nb] = int(input_num_targets)
-    res = torch.full(shape, fill_value, dtype=to_insert.dtype, device=to_insert.device,
-                     requires_grad=to_insert.requires_grad)
+    res = full_of_filler(shape, fill_value, to_insert.dtype, to_insert.device, to_insert.requires_grad)
     if input_indices.numel() == 0 or to_insert.numel() == 0 or res.numel() == 0:
         return res
     _scatter_into(res, to_insert, input_indices, input_nums_indices, nb, backward_accumulate,

@@ -138,6 +138,12 @@ def matched_pair_loss_sum(data_a, data_b, indices_a: RaggedBatch, indices_b: Rag
 
     Returns: ``[B]`` in the arithmetic dtype — float32, or float64 for float64 data (half-precision data are converted on
     load and accumulated in float32).  One kernel launch forward, one backward (+ one cast for half-precision gradients).
+
+    NaN and ±inf in matched rows give what float64 autograd of the composition gives: NaN / ±inf in the sums and in
+    the gradients where it has them (the smooth-L1 gradient at a NaN difference is NaN, the L1 gradient 0).  Rows no
+    pair reads — unmatched rows, the rows slots past the counts point at — never reach the result, whatever they hold:
+    their gradients are exactly 0.  For ``"iou_xyxy"`` this is pinned for NaN coordinates and special weights; at an
+    infinite box edge autograd's NaN pattern (``prod`` backward) is not mirrored.
     """
     if kind not in _KINDS:
         raise RuntimeError(f"kind must be one of {sorted(_KINDS)}")

@@ -146,8 +146,9 @@ def _resolve_dim(indices: RaggedBatch, dim_to_index_in: Optional[int], what: str
 def batched_indexing_access(input_data: Union[RaggedBatch, torch.Tensor], input_indices: RaggedBatch,
                             filler_value: float = 0.0, dim_to_index_in: Optional[int] = None) -> RaggedBatch:
     """Ragged gather: ``out[i, j] == input_data[i, input_indices[i, j]]`` for ``j < input_indices.sample_sizes[i]``
-    along ``dim_to_index_in`` (default: the indices' non-uniform dimension); ``filler_value`` in the padding.
-    Differentiable w.r.t. ``input_data`` (repeated indices accumulate).  Returns a RaggedBatch sharing the
+    along ``dim_to_index_in`` (default: the indices' non-uniform dimension); ``filler_value`` in the padding, converted as
+    ``static_cast<scalar_t>(double)`` (nearest even; out of range -> ±inf, e.g. -1e9 in float16; -0.0 and NaN kept).
+    Rows are copied bit for bit (NaN payloads included).  Differentiable w.r.t. ``input_data`` (repeated indices accumulate).  Returns a RaggedBatch sharing the
     indices' sample sizes.  GPU only."""
     data = input_data.tensor if isinstance(input_data, RaggedBatch) else input_data
     dim, swap = _resolve_dim(input_indices, dim_to_index_in, "input indices")
@@ -164,7 +165,7 @@ def batched_inverse_indexing_access(input_data: Union[RaggedBatch, torch.Tensor]
                                     output_num_targets: int, filler_value: float = 0.0,
                                     dim_to_index_in: Optional[int] = None) -> torch.Tensor:
     """Ragged scatter into a fresh tensor: ``out[i, output_indices[i, j]] == input_data[i, j]``, ``filler_value``
-    elsewhere; ``out.shape[dim_to_index_in] == output_num_targets``.  Indices of one sample must be unique.
+    elsewhere (converted as in ``batched_indexing_access``); ``out.shape[dim_to_index_in] == output_num_targets``.  Indices of one sample must be unique.
     Differentiable w.r.t. ``input_data``.  GPU only."""
     data = input_data.tensor if isinstance(input_data, RaggedBatch) else input_data
     dim, swap = _resolve_dim(output_indices, dim_to_index_in, "output indices")

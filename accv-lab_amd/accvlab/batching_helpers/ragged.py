@@ -274,7 +274,8 @@ class RaggedBatch:
         return w.expand(self._tensor.shape).contiguous()
 
     def with_padded_set_to(self, value_to_set: float) -> "RaggedBatch":
-        """Copy whose padding holds ``value_to_set`` (out of place)."""
+        """Copy whose padding holds ``value_to_set`` (out of place), converted as ``static_cast<scalar_t>(double)`` on
+        CPU and GPU alike: out of range -> ±inf for float types, -0.0 and NaN kept."""
         out = self.as_self_with_cloned_data()
         out.set_padded_to(value_to_set)
         return out

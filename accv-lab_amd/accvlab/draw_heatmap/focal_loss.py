@@ -119,6 +119,10 @@ def gaussian_focal_loss(logits: torch.Tensor, target: torch.Tensor, *, alpha: fl
     dtype of ``logits``; double backward is not supported); a ``target`` that requires grad is refused.  Neither
     direction synchronises with the host: one streaming kernel plus a one-block finishing kernel forward, one streaming
     kernel backward, all on torch's current stream.  The forward is bitwise reproducible (no atomics).
+
+    Special values follow float64 autograd of the definition: a NaN logit makes the loss NaN and its own gradient NaN
+    (so AMP's ``GradScaler`` skips the step), the clamp still gives exactly 0 gradient to finite logits outside
+    ``[eps, 1 - eps]``, and ±inf logits give a finite loss and a zero gradient.
     """
     _check(logits, target, alpha, gamma, avg_factor)
     return _GaussianFocalLoss.apply(logits, target, alpha, gamma, pos_weight, neg_weight, clamp_eps, avg_factor)

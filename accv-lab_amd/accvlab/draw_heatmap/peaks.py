@@ -65,8 +65,10 @@ def heatmap_peaks(heatmap: torch.Tensor, k: int, *, kernel: int = 3, per_class: 
     ``max_pool2d`` with padding ``kernel // 2``); every member of a plateau survives, suppressed elements score 0.  Per
     group the ``k`` largest ``s`` in descending order; equal scores come in ascending flat index of the group
     (class-major when ``per_class=False``) — exactly ``torch.sort(s, descending=True, stable=True)`` cut at ``k``, so a map
-    with fewer than ``k`` peaks is filled up deterministically with its first suppressed elements.  Maps with NaN or
-    infinities give unspecified (but in-bounds) results.
+    with fewer than ``k`` peaks is filled up deterministically with its first suppressed elements.  NaN and infinities
+    follow the same composition: the window maximum carries NaN through (as ``max_pool2d``), so a NaN scores NaN, its
+    finite neighbours score 0 and a suppressed ±inf scores NaN (``inf * 0``); every NaN, whatever its sign or payload,
+    ranks above +inf, NaNs among themselves by ascending index, and reads back as NaN.  -0.0 ties with +0.0.
 
     Returns: ``HeatmapPeaks(scores, indices, classes, ys, xs)``, each ``[B, k]`` (``[B, C, k]`` with ``per_class=True``).
     ``scores`` has the input dtype and holds the map's values exactly; ``indices`` (in-plane ``y * W + x``), ``classes``

@@ -171,7 +171,9 @@ template <bool INT_POW>
 __device__ __forceinline__ float focal_grad(float x, float t, const FocalParams& f)
 {
     const Sig z = sigmoid_clamped(x, f.clamp_eps);
-    if (!z.pass) return 0.0f;
+    // the clamp passes no gradient outside [eps, 1 - eps], but a NaN logit fails both comparisons: autograd multiplies
+    // that zero by the NaN sigmoid derivative, so the element's gradient is NaN (and AMP's inf / NaN check sees it)
+    if (!z.pass) return x != x ? x : 0.0f;
     if constexpr (INT_POW) {
         // at a positive (a = 1 - p):  d/dp [-log(p + 1e-12) (1 - p)^2] = -[(1 - p)^2 / (p + 1e-12) - 2 (1 - p) log(p + 1e-12)]
         // elsewhere (a = p):          d/dp [-log(1 - p + 1e-12) p^2] = +[p^2 / (1 - p + 1e-12) - 2 p log(1 - p + 1e-12)]

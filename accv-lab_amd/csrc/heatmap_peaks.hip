@@ -5,8 +5,12 @@
 //   out = the k largest s of each group in descending order, equal scores by ascending flat index in the group
 //         (= torch.sort(s, descending=True, stable=True)[:k]);  a group is a frame (C*H*W) or one (b, c) plane (H*W)
 //
+// NaN: the window maximum carries NaN through as max_pool2d does, so a NaN scores NaN, its finite neighbours are
+// suppressed to ±0 and a suppressed ±inf scores NaN (inf * 0).  torch.sort ranks NaN above +inf.
+//
 // Every element gets a unique 64-bit key: the high word is the order-preserving bit pattern of s (-0.0 folded onto +0.0
-// first, so suppressed negatives tie with real zeros), the low word 0xFFFFFFFF - index in group.  Larger key = earlier in
+// first, so suppressed negatives tie with real zeros; every NaN mapped to 0xFFFFFFFF, above +inf), the low word
+// 0xFFFFFFFF - index in group.  Larger key = earlier in
 // the output, and since no two keys are equal the top-k of the keys IS the definition: there are no ties left to resolve.
 // Key 0 is never a real key (the low word of a real one is > 0 because group sizes stay below 2^32 - 1): it marks an empty
 // candidate slot.
@@ -82,8 +86,13 @@ __device__ __forceinline__ float load_one(const void* __restrict__ p, long long 
     else return __uint_as_float((unsigned)static_cast<const unsigned short*>(p)[i] << 16);
 }
 
+// max_pool2d's window maximum: a NaN anywhere in the window makes it NaN (fmaxf would skip it).  One v_maximum3_f32
+// per two elements on gfx950, as v_max3_f32 for fmaxf.
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 __device__ __forceinline__ unsigned score_bits(float s)
 {
+    if (s != s) return 0xffffffffu;   // every NaN: one key above +inf (torch.sort puts NaN first), read back as NaN
     unsigned u = __float_as_uint(s);
     if (u == 0x80000000u) u = 0u;   // -0.0 ranks with +0.0
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void peaks_chunk_kernel(const void* __res
             const int e = e0 + u * kThreads;
             float m = v[u][0];
 #pragma unroll
-            for (int d = 1; d <= 2 * HALF; ++d) m = fmaxf(m, v[u][d]);
+            for (int d = 1; d <= 2 * HALF; ++d) m = nan_max(m, v[u][d]);
             if (e < na) s_vmax[e] = m, s_centre[e] = v[u][HALF];
         }
     }
@@ -229,9 +238,11 @@ __global__ __launch_bounds__(kThreads) void peaks_chunk_kernel(const void* __res
             const int a = r * AW + off + c;
             const int lo = (off + c - h > 0 ? -h : -(off + c)), hi = (off + c + h < AW ? h : AW - 1 - off - c);
             float m = -INFINITY;
-            for (int d = lo; d <= hi; ++d) m = fmaxf(m, s_vmax[a + d]);
+            for (int d = lo; d <= hi; ++d) m = nan_max(m, s_vmax[a + d]);
             const float v = s_centre[a];
-            const float s = v == m ? v : 0.0f;
+            // x * (x == max): a local maximum keeps its exact value, a suppressed element becomes v * 0 — ±0 for a
+            // finite one, NaN for ±inf and for NaN (whose window maximum is NaN, never equal)
+            const float s = v == m ? v : v * 0.0f;
             const long long idx = group_base + (r0 + r) * p.W + c0 + c;
             keys[j] = ((u64)score_bits(s) << 32) | (u64)(0xffffffffu - (unsigned)idx);
         }

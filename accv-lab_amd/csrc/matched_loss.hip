@@ -79,6 +79,7 @@ __device__ __forceinline__ A dloss_of(A d, A beta)
     if (KIND == kL1 || KIND == kOneHotL1) return d > A(0) ? A(1) : (d < A(0) ? A(-1) : A(0));
     if (KIND == kL2) return A(2) * d;
     const A ad = d < A(0) ? -d : d;
+    if (d != d) return d;   // NaN, as autograd of smooth_l1_loss gives (L1's sign() gives 0 there, L2's 2 d NaN)
     return ad < beta ? d / beta : (d > A(0) ? A(1) : A(-1));
 }
 
