@@ -38,6 +38,11 @@ FL_AVG_DEVICE = 2
 LSA_MAXIMIZE = 1
 LSA_THREADS_64 = 2
 LSA_THREADS_1024 = 4
+MC_ONE_MINUS_PROB = 0
+MC_NEG_PROB = 1
+MC_FOCAL = 2
+MC_LABELS_I64 = 1
+MC_CXCYWH = 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -96,6 +101,11 @@ SIGNATURES = {
     "accv_linear_assignment_workspace_bytes": (_sz, [_ll, _ll, _ll, _i]),
     "accv_linear_assignment": (_i, [_vp, _i, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "accv_linear_assignment_host": (_i, [_vp, _i, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _u, _vp, _vp, _vp, _vp]),
+    # matching-cost matrices (params: a MatchingCostParams by address)
+    "accv_matching_cost": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp,
+                                _vp]),
+    "accv_matching_cost_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp,
+                                     _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -122,6 +132,14 @@ SIGNATURES = {
     "accv_polyline_grad_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i]),
 }
 
+
+
+class MatchingCostParams(ctypes.Structure):
+    """accv_matching_cost_params of include/accv_hip.h"""
+    _fields_ = [(n, ctypes.c_double) for n in ("class_weight", "l1_weight", "iou_weight", "giou_weight", "focal_alpha",
+                                                "focal_gamma", "focal_eps", "iou_eps", "filler")]
+
+
 _lib = None
 _handle = None
 
@@ -136,7 +154,7 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 # entry points that BLOCK (wait for a native job, run a long host memcpy): they stay on ctypes, which drops the
 # interpreter lock for the duration of the call — the trampoline keeps it
 _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
-             "accv_polyline_grad_host", "accv_linear_assignment_host"}
+             "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host"}
 
 
 def _fast_entry(fn, res, args):

@@ -34,6 +34,7 @@ from .batched_processing_py import (
 
 from .fused import matched_pair_loss_sum  # (extension) gathers + per-object loss + masked sum in one launch
 from .assignment import batched_linear_sum_assignment  # (extension) per-frame Hungarian matching in one launch
+from .matching_cost import batched_matching_cost, batched_hungarian_match  # (extension) fused matching-cost matrices
 
 __version__ = "0.1.0"
 
@@ -44,10 +45,12 @@ __all__ = [
     "average_over_targets",
     "batched_bool_indexing",
     "batched_bool_indexing_write",
+    "batched_hungarian_match",
     "batched_index_mapping",
     "batched_indexing_access",
     "batched_indexing_write",
     "batched_linear_sum_assignment",
+    "batched_matching_cost",
     "batched_inverse_indexing_access",
     "combine_data",
     "get_compact_from_named_tuple",

@@ -71,6 +71,15 @@ def match_batched_on_device(gt_boxes: bh.RaggedBatch, gt_labels: bh.RaggedBatch,
     return gt_rb, pred_rb
 
 
+def match_batched_fused_cost(gt_boxes: bh.RaggedBatch, gt_labels: bh.RaggedBatch, pred_boxes, pred_scores, check=True):
+    """``match_batched_on_device`` with the cost matrices built by ``bh.batched_matching_cost`` (one launch: the class
+    term ``1 - p[q, l_g]`` plus ``1 - IoU``, the padded columns never computed) instead of the broadcast composition —
+    cost and assignment are two launches, with no host synchronisation when ``check=False``."""
+    pred_rb, gt_rb = bh.batched_hungarian_match(pred_scores, gt_labels, pred_boxes, gt_boxes, class_cost="one_minus_prob",
+                                                iou_weight=1.0, iou_eps=EPS, check=check)[:2]
+    return gt_rb, pred_rb
+
+
 def loss_batched(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, match_gt, match_pred):
     """Per-frame loss ``[B]`` = class L1 + (1 - IoU) over matched pairs + existence L1 over all predictions."""
     num_q, num_classes = pred_scores.shape[1], pred_scores.shape[2]
@@ -180,5 +189,16 @@ def run_batched_on_device(gt_boxes_l, gt_labels_l, gt_weights_l, pred_boxes, pre
     gt_labels = bh.combine_data(gt_labels_l, other_with_same_sample_sizes=gt_boxes)
     gt_weights = bh.combine_data(gt_weights_l, other_with_same_sample_sizes=gt_boxes)
     m_gt, m_pred = match_batched_on_device(gt_boxes, gt_labels, pred_boxes, pred_scores, check=check)
+    fn = loss_batched_fused if fused else loss_batched
+    return fn(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, m_gt, m_pred)
+
+
+def run_batched_fused_cost(gt_boxes_l, gt_labels_l, gt_weights_l, pred_boxes, pred_scores, pred_exist, fused=False,
+                           check=True):
+    """``run_batched`` with the matching done by ``match_batched_fused_cost``."""
+    gt_boxes = bh.combine_data(gt_boxes_l)
+    gt_labels = bh.combine_data(gt_labels_l, other_with_same_sample_sizes=gt_boxes)
+    gt_weights = bh.combine_data(gt_weights_l, other_with_same_sample_sizes=gt_boxes)
+    m_gt, m_pred = match_batched_fused_cost(gt_boxes, gt_labels, pred_boxes, pred_scores, check=check)
     fn = loss_batched_fused if fused else loss_batched
     return fn(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, m_gt, m_pred)

@@ -363,6 +363,52 @@ int accv_linear_assignment_host(const void* cost, int dtype, long long B, long l
                                 const long long* col_counts, unsigned flags, long long* row_ind, long long* col_ind,
                                 long long* sizes, int* status);
 
+/* ------------------------------------------------------------------------------------------------ matching costs
+ * The [B, Q, G] cost matrices of Hungarian matching in one launch (what accv_linear_assignment reads): replaces the
+ * broadcast chains and the per-object one-hot loop of packages/batching_helpers/example/matcher.py:22-31, 78-132.
+ * out[b, q, g] (contiguous, f32, f64 for dtype 3) is, for g < G_b = clamp(counts[b], 0, G) (counts: device int64 [B],
+ * NULL = G for every frame):
+ *     class_weight * cls + l1_weight * l1 + iou_weight * iou + giou_weight * giou     (summed in this order)
+ * and params->filler for G_b <= g < G.  A term whose weight is 0 is not evaluated and its pointers may be NULL.
+ *   cls (kind 0) 1 - p[q, l_g]; (kind 1) -p[q, l_g]; (kind 2) mmdet FocalLossCost with s = sigmoid(x[q, l_g]) and
+ *       1 - s from exp(-|x|):  (-log(s + eps)) * alpha * (1 - s)^gamma - (-log(1 - s + eps)) * (1 - alpha) * s^gamma;
+ *       a label outside [0, C) gives NaN
+ *   l1   sum over d < D of |bp_d - bg_d|
+ *   iou  1 - inter / max(union, iou_eps), intersection sides clamped at 0, areas not clamped
+ *   giou -GIoU with union and enclosing area floored at iou_eps (mmdet bbox_overlaps, mode "giou")
+ * IoU and GIoU need D == 4 and read xyxy boxes, or cxcywh boxes with ACCV_MC_CXCYWH (converted first); l1 reads the raw
+ * coordinates.  NaN in an evaluated input gives NaN for the pair; infinities follow the float64 formula.
+ * scores [B, Q, C] (element (b, q, c) at b * scores_stride_b + q * scores_stride_q + c), pred_boxes [B, Q, D] (the
+ * same with boxes_stride_b / boxes_stride_q): dtype 0 f32, 1 f16, 2 bf16, 3 f64 (the codes of accv_linear_assignment),
+ * strides in elements; gt_labels [B, G] int32 (int64 with ACCV_MC_LABELS_I64) and gt_boxes [B, G, D] of the same dtype,
+ * contiguous.  f16 / bf16 are widened exactly to f32 and evaluated in f32; f64 in f64.  D <= 16.  Returns ACCV_EINVAL
+ * (null params, negative size, unknown dtype, kind or flag, D > 16, IoU / GIoU with D != 4, a null pointer of an
+ * evaluated term or of out) before touching the device, ACCV_ELAUNCH if the launch fails; B * Q * G == 0 launches
+ * nothing.  No host synchronisation. */
+#define ACCV_MC_ONE_MINUS_PROB 0
+#define ACCV_MC_NEG_PROB 1
+#define ACCV_MC_FOCAL 2
+#define ACCV_MC_LABELS_I64 1u
+#define ACCV_MC_CXCYWH 2u
+/* the float parameters, host memory, read during the call (passed by pointer so the entry takes integers only) */
+typedef struct accv_matching_cost_params {
+    double class_weight, l1_weight, iou_weight, giou_weight;
+    double focal_alpha, focal_gamma, focal_eps, iou_eps;
+    double filler;
+} accv_matching_cost_params;
+int accv_matching_cost(const void* scores, const void* pred_boxes, const void* gt_labels, const void* gt_boxes,
+                       const long long* counts, int dtype, int kind, unsigned flags, long long B, long long Q,
+                       long long C, long long G, long long D, long long scores_stride_b, long long scores_stride_q,
+                       long long boxes_stride_b, long long boxes_stride_q, const accv_matching_cost_params* params,
+                       void* out, void* stream);
+/* The same on the host (same operation sequence: equal bits for every term but the focal one); every pointer is host
+ * memory.  Blocks the calling thread. */
+int accv_matching_cost_host(const void* scores, const void* pred_boxes, const void* gt_labels, const void* gt_boxes,
+                            const long long* counts, int dtype, int kind, unsigned flags, long long B, long long Q,
+                            long long C, long long G, long long D, long long scores_stride_b, long long scores_stride_q,
+                            long long boxes_stride_b, long long boxes_stride_q, const accv_matching_cost_params* params,
+                            void* out);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */
