@@ -43,6 +43,13 @@ MC_NEG_PROB = 1
 MC_FOCAL = 2
 MC_LABELS_I64 = 1
 MC_CXCYWH = 2
+CR_MAX_MAPS = 8
+CR_MAX_CHANNELS = 64
+CR_COUNTS_I64 = 1
+CR_INDEX_FORM = 2
+CR_WEIGHTS_PER_CHANNEL = 4
+CR_L1 = 0
+CR_SMOOTH_L1 = 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -106,6 +113,14 @@ SIGNATURES = {
                                 _vp]),
     "accv_matching_cost_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp,
                                      _vp]),
+    # centre-point regression (maps: host arrays of pointers and channel counts; params: a CenterRegressionParams by address)
+    "accv_gather_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
+    "accv_scatter_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
+    "accv_center_regression_loss_workspace_bytes": (_sz, [_ll]),
+    "accv_center_regression_loss": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _sz, _vp]),
+    "accv_center_regression_loss_bwd": (_i, [_vp, _vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp, _vp, _vp, _vp,
+                                             _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -138,6 +153,11 @@ class MatchingCostParams(ctypes.Structure):
     """accv_matching_cost_params of include/accv_hip.h"""
     _fields_ = [(n, ctypes.c_double) for n in ("class_weight", "l1_weight", "iou_weight", "giou_weight", "focal_alpha",
                                                 "focal_gamma", "focal_eps", "iou_eps", "filler")]
+
+
+class CenterRegressionParams(ctypes.Structure):
+    """accv_center_regression_params of include/accv_hip.h"""
+    _fields_ = [("kind", ctypes.c_int), ("avg_mode", ctypes.c_int), ("beta", ctypes.c_float), ("avg_factor", ctypes.c_float)]
 
 
 _lib = None

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "accv_common.h"
+#include "pointwise_loss_arith.h"
 
 namespace {
 
@@ -24,7 +25,7 @@ namespace {
 //   kIoUxyxy   (:240-274, _per_object_bbox_overlap_loss) rows are boxes (x0, y0, x1, y1): 1 - intersection / max(union, eps)
 //   kOneHotL1  (:37-43 class branch + :225-238) a holds integer class labels [B, w_a], b the scores [B, w_b, C]:
 //              sum_c |onehot(label)[c] - score[c]|
-enum Kind { kL1 = 0, kL2 = 1, kSmoothL1 = 2, kIoUxyxy = 3, kOneHotL1 = 4 };
+using namespace accv_loss;   // Kind and the element-wise loss_of / dloss_of (pointwise_loss_arith.h)
 enum DType { kF32 = 0, kF16 = 1, kBF16 = 2, kF64 = 3 };
 struct bf16_raw {
     uint16_t v;
@@ -63,24 +64,6 @@ __device__ __forceinline__ long long wrap_index(long long j, long long width)
 {
     if (j < 0) j += width;   // negative indices wrap once, as in the gather kernels (cu:75-77)
     return (j < 0 || j >= width) ? -1 : j;
-}
-
-template <int KIND, class A>
-__device__ __forceinline__ A loss_of(A d, A beta)
-{
-    const A ad = d < A(0) ? -d : d;
-    if (KIND == kL1 || KIND == kOneHotL1) return ad;
-    if (KIND == kL2) return d * d;
-    return ad < beta ? A(0.5) * d * d / beta : ad - A(0.5) * beta;   // torch.nn.functional.smooth_l1_loss
-}
-template <int KIND, class A>
-__device__ __forceinline__ A dloss_of(A d, A beta)
-{
-    if (KIND == kL1 || KIND == kOneHotL1) return d > A(0) ? A(1) : (d < A(0) ? A(-1) : A(0));
-    if (KIND == kL2) return A(2) * d;
-    const A ad = d < A(0) ? -d : d;
-    if (d != d) return d;   // NaN, as autograd of smooth_l1_loss gives (L1's sign() gives 0 there, L2's 2 d NaN)
-    return ad < beta ? d / beta : (d > A(0) ? A(1) : A(-1));
 }
 
 // 1 - IoU of two (x0, y0, x1, y1) boxes with the reference's clamps (negative intersection extents -> 0, union < eps -> eps);

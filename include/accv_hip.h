@@ -332,6 +332,69 @@ int accv_heatmap_peaks(const void* x, int dtype, long long B, long long C, long 
                        int per_class, void* scores, long long* indices, long long* classes, long long* ys, long long* xs,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ centre-point regression
+ * The regression branch of a centre-point head (CenterNet / CenterPoint: offset, size, height, rot, vel at the object
+ * centres) without the cat / permute / gather / scatter passes over the maps of mmdet's transpose_and_gather_feat.
+ *
+ * Maps: a HOST array `maps` of num_maps (1..ACCV_CR_MAX_MAPS) device pointers and a HOST array `channels` of their
+ * channel counts C_i >= 0; map i is [B, C_i, H, W] contiguous of dtype 0 f32, 1 f16, 2 bf16 (the codes of
+ * accv_gaussian_focal_loss), element-aligned.  Their channels are concatenated in the order given,
+ * C = sum C_i <= ACCV_CR_MAX_CHANNELS; H * W < 2^31; element offsets are 64-bit.
+ * Centres: int32 [B, N, 2] as (x, y) with `counts` [B] (int32, int64 with ACCV_CR_COUNTS_I64; clamped to [0, N]), or with
+ * ACCV_CR_INDEX_FORM int64 [B, N] in-plane indices y * W + x (counts is not read, every slot counts).  A slot is valid
+ * when it lies below its frame's count and its cell inside the map; nothing outside the maps is ever read.
+ * Every entry returns ACCV_EINVAL (negative size, unknown dtype / kind / flag / avg mode, more than ACCV_CR_MAX_MAPS maps
+ * or ACCV_CR_MAX_CHANNELS channels, H * W >= 2^31, null or misaligned pointers, null params) or ACCV_EWORKSPACE before
+ * touching the device, ACCV_ELAUNCH if a launch fails.  No atomics, no host synchronisation, bitwise reproducible. */
+#define ACCV_CR_MAX_MAPS 8
+#define ACCV_CR_MAX_CHANNELS 64
+#define ACCV_CR_COUNTS_I64 1u
+#define ACCV_CR_INDEX_FORM 2u
+#define ACCV_CR_WEIGHTS_PER_CHANNEL 4u /* weights are [B, N, C] instead of [B, N] */
+#define ACCV_CR_L1 0                   /* the kind codes of accv_matched_pair_reduce */
+#define ACCV_CR_SMOOTH_L1 2
+/* the scalar parameters of the loss, host memory, read during the call (by pointer so the entries take integers only) */
+typedef struct accv_center_regression_params {
+    int kind;         /* ACCV_CR_L1 or ACCV_CR_SMOOTH_L1 */
+    int avg_mode;     /* ACCV_FL_AVG_NUM_POS (max(number of valid slots, 1)), ACCV_FL_AVG_VALUE, ACCV_FL_AVG_DEVICE */
+    float beta;       /* smooth-L1 transition point, > 0 */
+    float avg_factor; /* the denominator of ACCV_FL_AVG_VALUE */
+} accv_center_regression_params;
+/* out[b, n, c] (contiguous [B, N, C], the maps' dtype) = maps[b, c, y, x] bit for bit at a valid slot, +0 elsewhere.
+ * One launch; B * N * C == 0 launches nothing. */
+int accv_gather_at_centers(const void* const* maps, const int* channels, int num_maps, int dtype, long long B, long long H,
+                           long long W, const void* centers, const void* counts, long long N, unsigned flags, void* out,
+                           void* stream);
+/* Its backward: writes every element of every gradient map exactly once — +0, and at each valid cell the sum over the
+ * frame's valid slots on that cell, in ascending slot order, of grad_rows[b, n, c] ([B, N, C] contiguous, the maps'
+ * dtype), accumulated in f32 and rounded once.  The gradient maps need no initialisation.  One launch; B == 0 launches
+ * nothing, N == 0 writes zeros. */
+int accv_scatter_at_centers(void* const* grad_maps, const int* channels, int num_maps, int dtype, long long B, long long H,
+                            long long W, const void* centers, const void* counts, long long N, unsigned flags,
+                            const void* grad_rows, void* stream);
+/* *out_loss = sum over valid (b, n) and c of w * l(maps[b, c, y, x] - targets[b, n, c]) / denom, *out_denom = denom (f32
+ * device scalars).  l is L1 or smooth-L1(beta) with torch's definitions; targets f32 [B, N, C]; weights NULL (1), f32
+ * [B, N] or, with ACCV_CR_WEIGHTS_PER_CHANNEL, [B, N, C]; rows of invalid slots are never read.  Arithmetic in f32
+ * (f16 / bf16 widened exactly), one f64 partial per frame, added in a fixed order by a second one-block launch.
+ * avg_factor_dev: the f32 device scalar of ACCV_FL_AVG_DEVICE.  ACCV_CR_INDEX_FORM is not taken.
+ * workspace: accv_center_regression_loss_workspace_bytes(B) bytes of device memory, 16-byte aligned.  B == 0 launches
+ * nothing (and writes nothing). */
+size_t accv_center_regression_loss_workspace_bytes(long long B);
+int accv_center_regression_loss(const void* const* maps, const int* channels, int num_maps, int dtype, long long B,
+                                long long H, long long W, const void* centers, const void* counts, long long N,
+                                unsigned flags, const float* targets, const float* weights_or_null,
+                                const accv_center_regression_params* params, const float* avg_factor_dev, float* out_loss,
+                                float* out_denom, void* workspace, size_t workspace_bytes, void* stream);
+/* Its backward, with the complete-write contract of accv_scatter_at_centers: the contribution of slot n to channel c of
+ * its cell is (w * dl/dd) * (*grad_out / *denom), evaluated in f32 in exactly this order; contributions to one cell add
+ * in ascending slot order in f32 and are rounded once to the maps' dtype.  grad_out and denom are f32 device scalars
+ * (denom: out_denom of the forward).  params->avg_mode and avg_factor are not read. */
+int accv_center_regression_loss_bwd(const void* const* maps, void* const* grad_maps, const int* channels, int num_maps,
+                                    int dtype, long long B, long long H, long long W, const void* centers,
+                                    const void* counts, long long N, unsigned flags, const float* targets,
+                                    const float* weights_or_null, const accv_center_regression_params* params,
+                                    const float* grad_out, const float* denom, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
