@@ -50,6 +50,8 @@ CR_INDEX_FORM = 2
 CR_WEIGHTS_PER_CHANNEL = 4
 CR_L1 = 0
 CR_SMOOTH_L1 = 2
+MF_IDX_I64 = 1
+MF_LABELS_I64 = 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -113,6 +115,16 @@ SIGNATURES = {
                                 _vp]),
     "accv_matching_cost_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp,
                                      _vp]),
+    # matched sigmoid focal loss (params: a MatchedFocalParams by address)
+    "accv_matched_focal_loss_workspace_bytes": (_sz, [_ll, _ll, _ll]),
+    "accv_matched_focal_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp,
+                                     _vp, _sz, _vp]),
+    "accv_matched_focal_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll,
+                                         _vp, _vp, _vp]),
+    "accv_matched_focal_loss_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp,
+                                          _vp]),
+    "accv_matched_focal_loss_bwd_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll,
+                                              _ll, _vp, _vp]),
     # centre-point regression (maps: host arrays of pointers and channel counts; params: a CenterRegressionParams by address)
     "accv_gather_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
     "accv_scatter_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
@@ -155,6 +167,12 @@ class MatchingCostParams(ctypes.Structure):
                                                 "focal_gamma", "focal_eps", "iou_eps", "filler")]
 
 
+class MatchedFocalParams(ctypes.Structure):
+    """accv_matched_focal_params of include/accv_hip.h"""
+    _fields_ = [("alpha", ctypes.c_double), ("gamma", ctypes.c_double), ("avg_factor", ctypes.c_double),
+                ("avg_mode", ctypes.c_int), ("avg_factor_dev", ctypes.c_void_p)]
+
+
 class CenterRegressionParams(ctypes.Structure):
     """accv_center_regression_params of include/accv_hip.h"""
     _fields_ = [("kind", ctypes.c_int), ("avg_mode", ctypes.c_int), ("beta", ctypes.c_float), ("avg_factor", ctypes.c_float)]
@@ -174,7 +192,8 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 # entry points that BLOCK (wait for a native job, run a long host memcpy): they stay on ctypes, which drops the
 # interpreter lock for the duration of the call — the trampoline keeps it
 _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
-             "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host"}
+             "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
+             "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host"}
 
 
 def _fast_entry(fn, res, args):

@@ -1,0 +1,235 @@
+"""(extension) Sigmoid focal classification loss of a set-prediction head (DETR / StreamPETR / Focal head) over ALL
+queries against the labels of the matched ground truth — the last link of the loss chain after
+``batched_matching_cost``, ``batched_linear_sum_assignment`` and ``matched_pair_loss_sum``.
+
+The torch composition gathers the labels through ``gt_ind``, writes them into a ``[B, Q]`` label tensor filled with the
+background id, builds a ``[B, Q, C]`` one-hot target and runs a dozen element-wise launches forward and about twice that
+backward.  Here the target is derived in the kernel: two launches forward, one write-only launch backward.
+
+GPU tensors run the HIP kernels (``accv_matched_focal_loss`` / ``_bwd``); CPU tensors run the host implementation of the
+same operation sequence (``accv_matched_focal_loss_host`` / ``_bwd_host``).  There is no CPU fallback for GPU tensors.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Union
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from .. import _amd_native as _nat
+from .ragged import RaggedBatch
+
+__all__ = ["matched_focal_loss"]
+
+_WHO = "matched_focal_loss"
+_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_PARAMS = {}   # (alpha, gamma, mode, value) -> MatchedFocalParams without a device pointer
+
+
+def _params(alpha, gamma, mode, value, avg_dev):
+    if avg_dev is not None:   # carries a pointer: not shared between calls
+        return _nat.MatchedFocalParams(alpha, gamma, value, mode, avg_dev.data_ptr())
+    key = (alpha, gamma, mode, value)
+    p = _PARAMS.get(key)
+    if p is None:
+        if len(_PARAMS) >= 64:
+            _PARAMS.clear()
+        p = _PARAMS[key] = _nat.MatchedFocalParams(alpha, gamma, value, mode, None)
+    return p
+
+
+class _Call:
+    """what the forward and the backward C-ABI calls of one invocation share"""
+
+    def __init__(self, logits, labels, pind, gind, counts, weights, params, avg_dev):
+        self.labels, self.pind, self.gind, self.counts, self.weights = labels, pind, gind, counts, weights
+        self.params, self.avg_dev = params, avg_dev
+        self.dev = logits.device
+        self.B, self.Q, self.C = (int(v) for v in logits.shape)
+        self.G, self.K = int(labels.shape[1]), int(pind.shape[1])
+        self.flags = (_nat.MF_IDX_I64 if pind.dtype == torch.int64 else 0) | \
+                     (_nat.MF_LABELS_I64 if labels.dtype == torch.int64 else 0)
+        self.out_dtype = torch.float64 if logits.dtype == torch.float64 else torch.float32
+
+    def inputs(self, logits):
+        return (logits.data_ptr(), self.labels.data_ptr(), self.pind.data_ptr(), self.gind.data_ptr(),
+                self.counts.data_ptr(), None if self.weights is None else self.weights.data_ptr())
+
+    def shape(self, logits):
+        # a dimension of extent 1 may carry any stride
+        sb = logits.stride(0) if self.B > 1 else self.Q * max(logits.stride(1), self.C)
+        sq = logits.stride(1) if self.Q > 1 else self.C
+        return (_DTYPES[logits.dtype], self.flags, self.B, self.Q, self.C, self.G, self.K, sb, sq,
+                ctypes.addressof(self.params))
+
+
+class _MatchedFocalLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, call, logits):
+        dev = call.dev
+        n = call.B * call.Q * call.C
+        out = (torch.empty if n > 0 else torch.zeros)((call.B,), dtype=call.out_dtype, device=dev)
+        denom = torch.empty((), dtype=torch.float64, device=dev)
+        if n > 0:
+            lib = _nat.lib()
+            if dev.type == "cuda":
+                nbytes = lib.accv_matched_focal_loss_workspace_bytes(call.B, call.Q, call.C)
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                with _nat.device_guard(dev):
+                    _nat.check(lib.accv_matched_focal_loss(*call.inputs(logits), *call.shape(logits), out.data_ptr(),
+                                                           denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
+            else:
+                _nat.check(lib.accv_matched_focal_loss_host(*call.inputs(logits), *call.shape(logits), out.data_ptr(),
+                                                            denom.data_ptr()), _WHO)
+        ctx.call = call
+        ctx.save_for_backward(logits, denom)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        call = ctx.call
+        logits, denom = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        grad = torch.empty(logits.shape, dtype=logits.dtype, device=call.dev)   # contiguous, written completely
+        if grad.numel() > 0:
+            grad_out = grad_out.to(call.out_dtype).contiguous()
+            lib = _nat.lib()
+            args = (*call.inputs(logits), grad_out.data_ptr(), denom.data_ptr(), *call.shape(logits), grad.data_ptr())
+            if call.dev.type == "cuda":
+                with _nat.device_guard(call.dev):
+                    _nat.check(lib.accv_matched_focal_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
+            else:
+                _nat.check(lib.accv_matched_focal_loss_bwd_host(*args), _WHO + " backward")
+        return None, grad
+
+
+def _ragged(name, rb, what):
+    if not isinstance(rb, RaggedBatch):
+        raise TypeError(f"{_WHO}: {name} must be a RaggedBatch {what}, got {type(rb).__name__}")
+    t = rb.tensor
+    if rb.num_batch_dims != 1 or t.dim() != 2 or rb.non_uniform_dim != 1:
+        raise ValueError(f"{_WHO}: {name} must be a RaggedBatch {what} with non_uniform_dim 1, got shape {tuple(t.shape)}, "
+                         f"non_uniform_dim {rb.non_uniform_dim}")
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{_WHO}: {name} must be int32 or int64, got {t.dtype}")
+    return t.detach().contiguous()
+
+
+def matched_focal_loss(pred_logits: torch.Tensor, gt_labels: RaggedBatch, pred_ind: RaggedBatch, gt_ind: RaggedBatch, *,
+                       alpha: float = 0.25, gamma: float = 2.0, query_weights: Optional[torch.Tensor] = None,
+                       avg_factor: Optional[Union[float, torch.Tensor]] = None) -> torch.Tensor:
+    """Per-frame sigmoid focal loss ``[B]`` of all ``Q x C`` logits of a frame, where a matched query's target is the
+    one-hot of its ground-truth label and every other query is background, divided by the number of matched pairs.
+
+    Args:
+        pred_logits: dense ``[B, Q, C]``, float32 / float16 / bfloat16 / float64.  Unit stride in the last dimension; the
+            batch and query strides are free (``cls_scores[..., :C]`` of a wider tensor needs no copy).
+        gt_labels: RaggedBatch ``[B, G*]``, int32 / int64.
+        pred_ind, gt_ind: RaggedBatch ``[B, K]``, int32 / int64, one dtype — what ``batched_linear_sum_assignment`` /
+            ``batched_hungarian_match`` return.  ONLY ``pred_ind.sample_sizes`` is read (on the device, clamped to
+            ``[0, K]``); comparing the two would cost a synchronisation.
+        alpha: weight of the positives, ``1 - alpha`` of the negatives; ``alpha < 0`` switches the blend off
+            (torchvision's convention).
+        gamma: focusing exponent, ``>= 0``.  2 runs as multiplications, other values through ``pow`` with
+            ``torch.pow``'s semantics (``gamma == 0`` included).
+        query_weights: optional dense ``[B, Q]`` of the logits dtype (mmdet's ``label_weights``); multiplies all ``C``
+            terms of a query.  No gradient flows to it.
+        avg_factor: ``None`` divides by ``max(M, 1)`` with ``M`` the number of pairs, ``sum_b clamp(n_b, 0, K)``, counted
+            on the device (DETR's ``num_boxes``); a Python number is used as given (``1.0`` gives raw sums); a 0-d float32
+            tensor on the logits' device (an all-reduced count) is read on the device.  No gradient flows to it.
+
+    Definition (torchvision's ``sigmoid_focal_loss`` / mmdet's ``py_sigmoid_focal_loss`` on one-hot targets; its float64
+    evaluation on the dtype-rounded inputs is what the tests pin)::
+
+        t = zeros(B, Q, C)
+        for b, j < clamp(n_b, 0, K):                       # ascending j
+            q, g = pred_ind[b, j], gt_ind[b, j]
+            if 0 <= q < Q and 0 <= g < G_max and no lower j named q:      # a pair with both indices in range names q
+                l = gt_labels[b, g]
+                if 0 <= l < C: t[b, q, l] = 1              # any other label: the query's row stays all-background
+        p = x.sigmoid(); ce = binary_cross_entropy_with_logits(x, t, reduction="none")
+        loss = ce * (1 - (p * t + (1 - p) * (1 - t))) ** gamma
+        if alpha >= 0: loss = (alpha * t + (1 - alpha) * (1 - t)) * loss
+        if query_weights is not None: loss = loss * query_weights[..., None]
+        out = loss.sum((1, 2)) / factor
+
+    Indices outside their range are skipped, not wrapped; a label outside ``[0, C)`` means background (mmdet's "label
+    C"); a query named twice takes the pair in the lowest slot; slots at or past ``n_b`` are never read.  A frame without
+    pairs is all background.  ``B``, ``Q`` or ``C`` of 0 give zeros and launch nothing.
+
+    Returns ``[B]`` float32 (float64 for float64 logits), so that it adds to what ``matched_pair_loss_sum`` returns.
+    Differentiable w.r.t. ``pred_logits`` only (no double backward); the gradient has the logits' dtype and is contiguous.
+    float16 / bfloat16 logits are widened exactly and evaluated in float32, float64 in float64; ``s``, ``1 - s`` and both
+    softplus values come from ``exp(-|x|)`` without cancellation; sums are accumulated in float64 in a fixed order, so
+    forward and backward are bitwise reproducible.  Two launches forward, one backward (every gradient element written
+    exactly once: no zero fill, no atomics), on torch's current stream, without host synchronisation or read-back: both
+    directions can be captured into a graph.
+
+    Special values: a NaN logit makes its frame's sum and its own gradient NaN, all other gradients stay finite.  A
+    logit of ``+inf`` gives ``+inf`` loss and gradient ``1 - alpha`` as a negative, 0 and -0 as a positive; ``-inf`` gives
+    ``+inf`` and ``-alpha`` as a positive, 0 and 0 as a negative (the limits; the float64 composition has ``inf * 0``
+    there).
+    """
+    if not isinstance(pred_logits, torch.Tensor):
+        raise TypeError(f"{_WHO}: pred_logits must be a tensor, got {type(pred_logits).__name__}")
+    if pred_logits.dim() != 3:
+        raise ValueError(f"{_WHO}: pred_logits must be [B, Q, C], got shape {tuple(pred_logits.shape)}")
+    if pred_logits.dtype not in _DTYPES:
+        raise TypeError(f"{_WHO}: pred_logits must be float32, float16, bfloat16 or float64, got {pred_logits.dtype}")
+    if pred_logits.shape[-1] > 1 and pred_logits.stride(-1) != 1:
+        raise ValueError(f"{_WHO}: the last dimension of pred_logits must have unit stride, got stride "
+                         f"{pred_logits.stride(-1)}")
+    dev = pred_logits.device
+    if dev.type not in ("cuda", "cpu"):
+        raise RuntimeError(f"{_WHO}: unsupported device {dev}")
+    B, Q, C = (int(v) for v in pred_logits.shape)
+    if Q > 1 and C > 0 and pred_logits.stride(1) < C or B > 1 and pred_logits.stride(0) < 0:
+        raise ValueError(f"{_WHO}: overlapping or reversed pred_logits (strides {pred_logits.stride()}) are not supported")
+    alpha, gamma = float(alpha), float(gamma)
+    if not gamma >= 0.0:
+        raise ValueError(f"{_WHO}: gamma must be >= 0, got {gamma}")
+    if alpha != alpha:
+        raise ValueError(f"{_WHO}: alpha is NaN")
+
+    labels = _ragged("gt_labels", gt_labels, "[B, G*]")
+    pind = _ragged("pred_ind", pred_ind, "[B, K]")
+    gind = _ragged("gt_ind", gt_ind, "[B, K]")
+    if pind.dtype != gind.dtype:
+        raise TypeError(f"{_WHO}: pred_ind is {pind.dtype}, gt_ind {gind.dtype}: one index dtype expected")
+    if pind.shape != gind.shape:
+        raise ValueError(f"{_WHO}: pred_ind has shape {tuple(pind.shape)}, gt_ind {tuple(gind.shape)}")
+    sizes = pred_ind.sample_sizes
+    if sizes.dim() != 1 or sizes.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{_WHO}: pred_ind.sample_sizes must be int32 or int64 [B]")
+    weights = query_weights
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (B, Q):
+            raise ValueError(f"{_WHO}: query_weights must be a tensor [B, Q] = [{B}, {Q}], got "
+                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+        if weights.dtype != pred_logits.dtype:
+            raise TypeError(f"{_WHO}: query_weights is {weights.dtype}, pred_logits {pred_logits.dtype}")
+        weights = weights.detach().contiguous()
+    for name, t in (("gt_labels", labels), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", sizes),
+                    ("query_weights", weights)):
+        if t is None:
+            continue
+        if t.device != dev:
+            raise ValueError(f"{_WHO}: {name} is on {t.device}, pred_logits on {dev}")
+        if int(t.shape[0]) != B:
+            raise ValueError(f"{_WHO}: {name} has batch size {t.shape[0]}, pred_logits {B}")
+
+    avg_dev = None
+    if avg_factor is None:
+        mode, value = _nat.FL_AVG_NUM_POS, 0.0
+    elif isinstance(avg_factor, torch.Tensor):
+        if not (avg_factor.dim() == 0 and avg_factor.dtype == torch.float32 and avg_factor.device == dev):
+            raise ValueError(f"{_WHO}: a tensor avg_factor must be a 0-d float32 tensor on the logits' device")
+        mode, value, avg_dev = _nat.FL_AVG_DEVICE, 0.0, avg_factor.detach()
+    else:
+        mode, value = _nat.FL_AVG_VALUE, float(avg_factor)
+    counts = sizes.detach().to(torch.int64).contiguous()
+    call = _Call(pred_logits, labels, pind, gind, counts, weights, _params(alpha, gamma, mode, value, avg_dev), avg_dev)
+    return _MatchedFocalLoss.apply(call, pred_logits)

@@ -202,3 +202,30 @@ def run_batched_fused_cost(gt_boxes_l, gt_labels_l, gt_weights_l, pred_boxes, pr
     m_gt, m_pred = match_batched_fused_cost(gt_boxes, gt_labels, pred_boxes, pred_scores, check=check)
     fn = loss_batched_fused if fused else loss_batched
     return fn(gt_boxes, gt_labels, gt_weights, pred_boxes, pred_scores, pred_exist, m_gt, m_pred)
+
+
+# ------------------------------------------------------------------------------------------------ focal class loss
+def focal_class_loss_composed(pred_logits, gt_labels: bh.RaggedBatch, pred_ind: bh.RaggedBatch, gt_ind: bh.RaggedBatch,
+                              alpha=0.25, gamma=2.0):
+    """The classification loss a DETR-style head trains with, per frame ``[B]``, as the composition a user writes from
+    the ragged operators and torch: the matched labels gathered through ``gt_ind`` and written through ``pred_ind`` into a
+    ``[B, Q]`` label tensor filled with the background id ``C``, a one-hot target, torchvision's ``sigmoid_focal_loss``
+    over all ``[B, Q, C]`` logits, divided by the number of matched pairs."""
+    B, Q, C = pred_logits.shape
+    matched_labels = bh.batched_indexing_access(gt_labels, gt_ind)
+    background = torch.full((B, Q), C, dtype=matched_labels.tensor.dtype, device=pred_logits.device)
+    query_labels = bh.batched_indexing_write(matched_labels, pred_ind, background)
+    t = torch.nn.functional.one_hot(query_labels.to(torch.int64), C + 1)[..., :C].to(pred_logits.dtype)
+    p = pred_logits.sigmoid()
+    ce = torch.nn.functional.binary_cross_entropy_with_logits(pred_logits, t, reduction="none")
+    loss = ce * (1 - (p * t + (1 - p) * (1 - t))) ** gamma
+    if alpha >= 0:
+        loss = (alpha * t + (1 - alpha) * (1 - t)) * loss
+    num_pos = pred_ind.sample_sizes.sum().clamp(min=1)
+    return loss.sum((1, 2)) / num_pos
+
+
+def focal_class_loss_fused(pred_logits, gt_labels: bh.RaggedBatch, pred_ind: bh.RaggedBatch, gt_ind: bh.RaggedBatch,
+                           alpha=0.25, gamma=2.0):
+    """The same loss through ``bh.matched_focal_loss``: two launches forward, one backward, no one-hot target."""
+    return bh.matched_focal_loss(pred_logits, gt_labels, pred_ind, gt_ind, alpha=alpha, gamma=gamma)

@@ -472,6 +472,65 @@ int accv_matching_cost_host(const void* scores, const void* pred_boxes, const vo
                             long long boxes_stride_b, long long boxes_stride_q, const accv_matching_cost_params* params,
                             void* out);
 
+/* ------------------------------------------------------------------------------------------------ matched focal loss
+ * The sigmoid focal classification loss of a set-prediction head over ALL queries against the labels of the matched
+ * ground truth (torchvision sigmoid_focal_loss / mmdet py_sigmoid_focal_loss on one-hot targets), without the [B, Q, C]
+ * one-hot target and the dozen element-wise launches of the torch composition:
+ *     out[b] = sum over q, c of  w[b, q] * l(x[b, q, c], c == label_b(q)) / denom
+ *     l(x, positive) = alpha (1 - s)^gamma softplus(-x),  l(x, negative) = (1 - alpha) s^gamma softplus(x),  s = sigmoid(x)
+ * alpha < 0 switches the alpha blend off; gamma >= 0 (2 runs as a multiplication, other values through pow).
+ * label_b(q): the pairs of frame b are the slots j < n_b = clamp(counts[b], 0, K) (counts: int64 [B]) of pred_ind /
+ * gt_ind [B, K] (int32, int64 with ACCV_MF_IDX_I64).  A pair names its query when 0 <= pred_ind < Q and 0 <= gt_ind < G;
+ * other pairs are skipped (no wrapping).  The LOWEST slot that names q decides: label_b(q) = gt_labels[b, gt_ind[b, j]]
+ * ([B, G] int32, int64 with ACCV_MF_LABELS_I64) when that lies in [0, C); otherwise, and for a query no pair names, every
+ * class of q is a negative.  Slots at or past n_b are never read.
+ * logits [B, Q, C] of dtype 0 f32, 1 f16, 2 bf16, 3 f64 (the codes of accv_matching_cost): element (b, q, c) at
+ * b * stride_b + q * stride_q + c, strides in elements, stride_q >= C.  query_weights: NULL or contiguous [B, Q] of the
+ * logits dtype.  f16 / bf16 are widened exactly and evaluated in f32, f64 in f64; sums are accumulated in f64.
+ * denom: max(sum_b n_b, 1) (ACCV_FL_AVG_NUM_POS), params->avg_factor (ACCV_FL_AVG_VALUE) or *params->avg_factor_dev
+ * (ACCV_FL_AVG_DEVICE, an f32 scalar in device memory; host memory for the host entry points).
+ * out [B] f32 (f64 for dtype 3); out_denom one f64 scalar that the backward reads.  workspace:
+ * accv_matched_focal_loss_workspace_bytes(B, Q, C) bytes of device memory, 16-byte aligned.  Two launches, no atomics
+ * on global memory, no host synchronisation, bitwise reproducible.  Returns ACCV_EINVAL (null params, negative size,
+ * unknown dtype / flag / avg mode, gamma < 0 or NaN, C or K above 2^31 - 1, stride_q < C, null or misaligned pointers) or
+ * ACCV_EWORKSPACE before touching the device, ACCV_ELAUNCH if a launch fails.  B * Q * C == 0 launches nothing and
+ * writes nothing. */
+#define ACCV_MF_IDX_I64 1u
+#define ACCV_MF_LABELS_I64 2u
+/* the scalar parameters, host memory, read during the call (by pointer so the entries take integers only) */
+typedef struct accv_matched_focal_params {
+    double alpha, gamma;
+    double avg_factor;           /* the denominator of ACCV_FL_AVG_VALUE */
+    int avg_mode;                /* ACCV_FL_AVG_NUM_POS, ACCV_FL_AVG_VALUE or ACCV_FL_AVG_DEVICE; the backward ignores it */
+    const float* avg_factor_dev; /* the f32 scalar of ACCV_FL_AVG_DEVICE */
+} accv_matched_focal_params;
+size_t accv_matched_focal_loss_workspace_bytes(long long B, long long Q, long long C);
+int accv_matched_focal_loss(const void* logits, const void* gt_labels, const void* pred_ind, const void* gt_ind,
+                            const long long* counts, const void* query_weights_or_null, int dtype, unsigned flags,
+                            long long B, long long Q, long long C, long long G, long long K, long long stride_b,
+                            long long stride_q, const accv_matched_focal_params* params, void* out, double* out_denom,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* Its backward: grad_logits (contiguous [B, Q, C], the logits dtype, round to nearest even) is written completely, every
+ * element exactly once: (w[b, q] * dl/dx) * (grad_out[b] / *denom), the scale formed in f64 and rounded to the
+ * arithmetic type.  grad_out [B] has the dtype of out, denom is out_denom of the forward.  One launch; needs no
+ * initialised gradient, uses no atomics. */
+int accv_matched_focal_loss_bwd(const void* logits, const void* gt_labels, const void* pred_ind, const void* gt_ind,
+                                const long long* counts, const void* query_weights_or_null, const void* grad_out,
+                                const double* denom, int dtype, unsigned flags, long long B, long long Q, long long C,
+                                long long G, long long K, long long stride_b, long long stride_q,
+                                const accv_matched_focal_params* params, void* grad_logits, void* stream);
+/* The same on the host (same operation sequence per element; a frame's sum is accumulated in element order); every
+ * pointer is host memory.  Block the calling thread. */
+int accv_matched_focal_loss_host(const void* logits, const void* gt_labels, const void* pred_ind, const void* gt_ind,
+                                 const long long* counts, const void* query_weights_or_null, int dtype, unsigned flags,
+                                 long long B, long long Q, long long C, long long G, long long K, long long stride_b,
+                                 long long stride_q, const accv_matched_focal_params* params, void* out, double* out_denom);
+int accv_matched_focal_loss_bwd_host(const void* logits, const void* gt_labels, const void* pred_ind, const void* gt_ind,
+                                     const long long* counts, const void* query_weights_or_null, const void* grad_out,
+                                     const double* denom, int dtype, unsigned flags, long long B, long long Q, long long C,
+                                     long long G, long long K, long long stride_b, long long stride_q,
+                                     const accv_matched_focal_params* params, void* grad_logits);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */

@@ -39,7 +39,7 @@ restore_only_exts
 
 echo "== pass 2: host side of libaccv_hip.so under clang ASan"
 RT="$(find /opt/rocm/lib/llvm -name 'libclang_rt.asan-x86_64.so' | head -1)"
-for f in accv_common draw_heatmap matched_loss polyline ragged_ops tensor_copier; do
+for f in $(cd "$PKG/csrc" && ls *.hip | sed 's/\.hip$//'); do   # every source: the library must export every declared symbol
     /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -I"$ROOT/include" -I"$PKG/csrc" -fno-gpu-rdc -pthread \
         -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -c "$PKG/csrc/$f.hip" -o "$TMP/lib/$f.o" &
 done
