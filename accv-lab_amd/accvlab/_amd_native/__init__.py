@@ -264,6 +264,40 @@ def check(status: int, what: str = "") -> None:
         raise AccvNativeError(f"{what}: {msg.decode() if msg else 'error'} (status {status})")
 
 
+def __getattr__(name):
+    # FLOAT_DTYPE_CODES: torch dtype -> dtype code of the loss-side entry points (accv::DType in csrc/accv_numeric.h).  An
+    # operator that does not take float64 refuses it itself.  Built on first use, so importing this module needs no torch.
+    if name == "FLOAT_DTYPE_CODES":
+        import torch
+
+        codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+        globals()[name] = codes
+        return codes
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def avg_factor_args(avg_factor, device, who: str, exc, where: str):
+    """`avg_factor` of a mean-reduced loss as (mode, value, device tensor or None): None counts on the device, a number is
+    passed by value, a 0-d float32 tensor on `device` is read on the device.  A wrong tensor raises `exc`; `where` names
+    the device in the message ("the logits' device")."""
+    import torch
+
+    if avg_factor is None:
+        return FL_AVG_NUM_POS, 0.0, None
+    if isinstance(avg_factor, torch.Tensor):
+        if not (avg_factor.dim() == 0 and avg_factor.dtype == torch.float32 and avg_factor.device == device):
+            raise exc(f"{who}: a tensor avg_factor must be a 0-d float32 tensor on {where}")
+        return FL_AVG_DEVICE, 0.0, avg_factor.detach()
+    return FL_AVG_VALUE, float(avg_factor), None
+
+
+def workspace(nbytes: int, device):
+    """Uninitialised scratch memory for one native call (torch's allocator aligns it to more than the 16 bytes needed)."""
+    import torch
+
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
 def last_dispatch() -> str:
     """Kernel instantiation + launch geometry of the last draw_heatmap call on this thread."""
     s = ctypes_lib().accv_draw_heatmap_last_dispatch()

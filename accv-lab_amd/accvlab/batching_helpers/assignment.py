@@ -17,7 +17,7 @@ from .data_format import RaggedBatch
 
 __all__ = ["batched_linear_sum_assignment"]
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 MAX_LARGE = 4096   # max(R, C) of the padded shape
 MAX_SMALL = 1024   # min(R, C) of the padded shape
 _MSG = {1: "cost matrix is infeasible", 2: "matrix contains invalid numeric entries"}   # scipy's texts
@@ -109,8 +109,7 @@ def batched_linear_sum_assignment(cost, *, maximize: bool = False, check: bool =
                 row.data_ptr(), col.data_ptr(), sizes.data_ptr(), status.data_ptr())
         lib = _nat.lib()
         if x.is_cuda:
-            ws = torch.empty((lib.accv_linear_assignment_workspace_bytes(B, R, C, _DTYPES[x.dtype]),), dtype=torch.uint8,
-                             device=dev)
+            ws = _nat.workspace(lib.accv_linear_assignment_workspace_bytes(B, R, C, _DTYPES[x.dtype]), dev)
             with _nat.device_guard(dev):
                 _nat.check(lib.accv_linear_assignment(*args, ws.data_ptr(), ws.numel(), _nat.stream_ptr(dev)),
                            "batched_linear_sum_assignment")

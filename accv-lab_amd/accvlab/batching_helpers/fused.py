@@ -25,7 +25,7 @@ from .. import _amd_native as _nat
 from .ragged import RaggedBatch
 
 _KINDS = {"l1": 0, "l2": 1, "smooth_l1": 2, "iou_xyxy": 3, "onehot_l1": 4}
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 _ONEHOT = _KINDS["onehot_l1"]
 
 

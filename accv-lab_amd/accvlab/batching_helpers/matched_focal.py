@@ -23,7 +23,7 @@ from .ragged import RaggedBatch
 __all__ = ["matched_focal_loss"]
 
 _WHO = "matched_focal_loss"
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 _PARAMS = {}   # (alpha, gamma, mode, value) -> MatchedFocalParams without a device pointer
 
 
@@ -75,7 +75,7 @@ class _MatchedFocalLoss(torch.autograd.Function):
             lib = _nat.lib()
             if dev.type == "cuda":
                 nbytes = lib.accv_matched_focal_loss_workspace_bytes(call.B, call.Q, call.C)
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                ws = _nat.workspace(nbytes, dev)
                 with _nat.device_guard(dev):
                     _nat.check(lib.accv_matched_focal_loss(*call.inputs(logits), *call.shape(logits), out.data_ptr(),
                                                            denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
@@ -221,15 +221,7 @@ def matched_focal_loss(pred_logits: torch.Tensor, gt_labels: RaggedBatch, pred_i
         if int(t.shape[0]) != B:
             raise ValueError(f"{_WHO}: {name} has batch size {t.shape[0]}, pred_logits {B}")
 
-    avg_dev = None
-    if avg_factor is None:
-        mode, value = _nat.FL_AVG_NUM_POS, 0.0
-    elif isinstance(avg_factor, torch.Tensor):
-        if not (avg_factor.dim() == 0 and avg_factor.dtype == torch.float32 and avg_factor.device == dev):
-            raise ValueError(f"{_WHO}: a tensor avg_factor must be a 0-d float32 tensor on the logits' device")
-        mode, value, avg_dev = _nat.FL_AVG_DEVICE, 0.0, avg_factor.detach()
-    else:
-        mode, value = _nat.FL_AVG_VALUE, float(avg_factor)
+    mode, value, avg_dev = _nat.avg_factor_args(avg_factor, dev, _WHO, ValueError, "the logits' device")
     counts = sizes.detach().to(torch.int64).contiguous()
     call = _Call(pred_logits, labels, pind, gind, counts, weights, _params(alpha, gamma, mode, value, avg_dev), avg_dev)
     return _MatchedFocalLoss.apply(call, pred_logits)

@@ -19,7 +19,7 @@ from .ragged import RaggedBatch
 
 __all__ = ["batched_matching_cost", "batched_hungarian_match"]
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 _KINDS = {"one_minus_prob": _nat.MC_ONE_MINUS_PROB, "neg_prob": _nat.MC_NEG_PROB, "focal": _nat.MC_FOCAL}
 _FORMATS = {"xyxy": 0, "cxcywh": _nat.MC_CXCYWH}
 MAX_BOX_DIM = 16

@@ -26,7 +26,7 @@ from torch.autograd.function import once_differentiable
 
 from .. import _amd_native as _nat
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 _KINDS = {"l1": _nat.CR_L1, "smooth_l1": _nat.CR_SMOOTH_L1}
 MAX_MAPS = _nat.CR_MAX_MAPS
 MAX_CHANNELS = _nat.CR_MAX_CHANNELS
@@ -53,7 +53,7 @@ def _check_feats(who, feats):
         if not m.is_contiguous():
             raise RuntimeError(f"{who}: feats[{i}] must be contiguous (a map is not copied silently)")
     first = maps[0]
-    if first.dtype not in _DTYPES:
+    if first.dtype not in _DTYPES or first.dtype == torch.float64:
         raise RuntimeError(f"{who}: feats must be float32, float16 or bfloat16, got {first.dtype}")
     for i, m in enumerate(maps[1:], 1):
         if m.dtype != first.dtype:
@@ -151,7 +151,7 @@ class _CenterRegressionLoss(torch.autograd.Function):
         flags = call.flags | (_nat.CR_WEIGHTS_PER_CHANNEL if weights is not None and weights.dim() == 3 else 0)
         if call.B > 0:
             lib = _nat.lib()
-            ws = torch.empty((lib.accv_center_regression_loss_workspace_bytes(call.B),), dtype=torch.uint8, device=dev)
+            ws = _nat.workspace(lib.accv_center_regression_loss_workspace_bytes(call.B), dev)
             ptrs = call.pointers(maps)
             with _nat.device_guard(dev):
                 _nat.check(lib.accv_center_regression_loss(
@@ -291,15 +291,7 @@ def center_regression_loss(feats: Union[torch.Tensor, Sequence[torch.Tensor]], c
             raise RuntimeError(f"{who}: {name} must be contiguous")
         if t.requires_grad:
             raise RuntimeError(f"{who}: no gradient flows to {name}; detach it")
-    if avg_factor is None:
-        mode, value = _nat.FL_AVG_NUM_POS, 0.0
-    elif isinstance(avg_factor, torch.Tensor):
-        if not (avg_factor.dim() == 0 and avg_factor.dtype == torch.float32 and avg_factor.device == first.device):
-            raise RuntimeError(f"{who}: a tensor avg_factor must be a 0-d float32 tensor on the maps' device")
-        mode, value = _nat.FL_AVG_DEVICE, 0.0
-        avg_factor = avg_factor.detach()
-    else:
-        mode, value = _nat.FL_AVG_VALUE, float(avg_factor)
+    mode, value, avg_factor = _nat.avg_factor_args(avg_factor, first.device, who, RuntimeError, "the maps' device")
     params = _nat.CenterRegressionParams(_KINDS[kind], mode, float(beta), value)
     call = _Call(maps, c_t, sizes, False)
     return _CenterRegressionLoss.apply(call, targets, weights, params, avg_factor, *maps)

@@ -25,10 +25,10 @@ from torch.autograd.function import once_differentiable
 
 from .. import _amd_native as _nat
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 
 
-def _check(logits, target, alpha, gamma, avg_factor):
+def _check(logits, target, alpha, gamma):
     for name, t in (("logits", logits), ("target", target)):
         if not isinstance(t, torch.Tensor):
             raise RuntimeError(f"gaussian_focal_loss: {name} must be a tensor")
@@ -36,7 +36,7 @@ def _check(logits, target, alpha, gamma, avg_factor):
             raise RuntimeError(f"gaussian_focal_loss: {name} must be contiguous (a heat map is not copied silently)")
         if not t.is_cuda:
             raise RuntimeError(f"gaussian_focal_loss: {name} must be a CUDA tensor (there is no CPU path)")
-    if logits.dtype not in _DTYPES:
+    if logits.dtype not in _DTYPES or logits.dtype == torch.float64:
         raise RuntimeError(f"gaussian_focal_loss: logits must be float32, float16 or bfloat16, got {logits.dtype}")
     if target.dtype != torch.float32:
         raise RuntimeError(f"gaussian_focal_loss: target must be float32, got {target.dtype}")
@@ -49,28 +49,21 @@ def _check(logits, target, alpha, gamma, avg_factor):
         raise RuntimeError("gaussian_focal_loss: no gradient flows to target; detach it")
     if not (alpha >= 1.0 and gamma >= 0.0):
         raise RuntimeError(f"gaussian_focal_loss: needs alpha >= 1 and gamma >= 0, got alpha={alpha}, gamma={gamma}")
-    if isinstance(avg_factor, torch.Tensor):
-        if not (avg_factor.dim() == 0 and avg_factor.dtype == torch.float32 and avg_factor.device == logits.device):
-            raise RuntimeError("gaussian_focal_loss: a tensor avg_factor must be a 0-d float32 tensor on the logits' device")
 
 
 class _GaussianFocalLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, alpha, gamma, pos_weight, neg_weight, clamp_eps, avg_factor):
+    def forward(ctx, logits, target, alpha, gamma, pos_weight, neg_weight, clamp_eps, avg):
         dev = logits.device
         n = logits.numel()
         loss = torch.zeros((), dtype=torch.float32, device=dev) if n == 0 else torch.empty((), dtype=torch.float32, device=dev)
         denom = torch.empty((), dtype=torch.float32, device=dev)
         params = (float(alpha), float(gamma), float(pos_weight), float(neg_weight), float(clamp_eps))
-        if avg_factor is None:
-            mode, value, dev_ptr = _nat.FL_AVG_NUM_POS, 0.0, None
-        elif isinstance(avg_factor, torch.Tensor):
-            mode, value, dev_ptr = _nat.FL_AVG_DEVICE, 0.0, avg_factor.data_ptr()
-        else:
-            mode, value, dev_ptr = _nat.FL_AVG_VALUE, float(avg_factor), None
+        mode, value, avg_dev = avg
+        dev_ptr = avg_dev.data_ptr() if avg_dev is not None else None
         if n > 0:
             lib = _nat.lib()
-            ws = torch.empty((lib.accv_gaussian_focal_loss_workspace_bytes(n),), dtype=torch.uint8, device=dev)
+            ws = _nat.workspace(lib.accv_gaussian_focal_loss_workspace_bytes(n), dev)
             with _nat.device_guard(dev):
                 _nat.check(lib.accv_gaussian_focal_loss(
                     logits.data_ptr(), target.data_ptr(), n, _DTYPES[logits.dtype], *params, mode, value, dev_ptr,
@@ -124,5 +117,6 @@ def gaussian_focal_loss(logits: torch.Tensor, target: torch.Tensor, *, alpha: fl
     (so AMP's ``GradScaler`` skips the step), the clamp still gives exactly 0 gradient to finite logits outside
     ``[eps, 1 - eps]``, and ±inf logits give a finite loss and a zero gradient.
     """
-    _check(logits, target, alpha, gamma, avg_factor)
-    return _GaussianFocalLoss.apply(logits, target, alpha, gamma, pos_weight, neg_weight, clamp_eps, avg_factor)
+    _check(logits, target, alpha, gamma)
+    avg = _nat.avg_factor_args(avg_factor, logits.device, "gaussian_focal_loss", RuntimeError, "the logits' device")
+    return _GaussianFocalLoss.apply(logits, target, alpha, gamma, pos_weight, neg_weight, clamp_eps, avg)

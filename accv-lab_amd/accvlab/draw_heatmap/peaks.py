@@ -21,7 +21,7 @@ import torch
 
 from .. import _amd_native as _nat
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_DTYPES = _nat.FLOAT_DTYPE_CODES
 _MAX_K = 1024
 
 
@@ -40,7 +40,7 @@ def _check(heatmap, k, kernel):
         raise RuntimeError("heatmap_peaks: heatmap must be a CUDA tensor (there is no CPU path)")
     if not heatmap.is_contiguous():
         raise RuntimeError("heatmap_peaks: heatmap must be contiguous (a heat map is not copied silently)")
-    if heatmap.dtype not in _DTYPES:
+    if heatmap.dtype not in _DTYPES or heatmap.dtype == torch.float64:
         raise RuntimeError(f"heatmap_peaks: heatmap must be float32, float16 or bfloat16, got {heatmap.dtype}")
     if heatmap.dim() not in (3, 4):
         raise RuntimeError(f"heatmap_peaks: heatmap must be [B, H, W] or [B, C, H, W], got {heatmap.dim()} dimensions")
@@ -104,7 +104,7 @@ def heatmap_peaks(heatmap: torch.Tensor, k: int, *, kernel: int = 3, per_class: 
         ws_bytes = lib.accv_heatmap_peaks_workspace_bytes(B, C, H, W, k)
         if ws_bytes == 0:
             raise RuntimeError(f"heatmap_peaks: map {B} x {C} x {H} x {W} is too large (groups below 2^32 - 1 elements)")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws = _nat.workspace(ws_bytes, dev)
         with _nat.device_guard(dev):
             _nat.check(lib.accv_heatmap_peaks(
                 heatmap.data_ptr(), _DTYPES[heatmap.dtype], B, C, H, W, kernel, k, 1 if per_class else 0,

@@ -30,11 +30,11 @@
 // "product, then sum" means exactly that.
 // Bandwidth / launch bound work: no MFMA.
 #include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
 
 #include <cstdint>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 #include "pointwise_loss_arith.h"
 
 #pragma clang fp contract(off)
@@ -46,35 +46,14 @@ using accv_loss::kL1;
 using accv_loss::kSmoothL1;
 using accv_loss::loss_of;
 
-enum DType { kF32 = 0, kF16 = 1, kBF16 = 2 };   // the codes of accv_gaussian_focal_loss
+using namespace accv;   // dtype codes (f64 is not taken here), Stored<DT>, load / store<DT>, block_sum, denominator
+
 constexpr int kThreads = 256;
 constexpr int kMaxMaps = ACCV_CR_MAX_MAPS;
 constexpr int kMaxChannels = ACCV_CR_MAX_CHANNELS;
 constexpr int kList = 2048;                     // slots of one band the LDS list holds; a band with more takes the slow path
-constexpr long long kMaxBlocks = 0x7fffffffll;
 
-// element types: f32 as float, f16 / bf16 as their 16 bits
-struct F32 {
-    using raw = float;
-    __device__ static float widen(raw v) { return v; }
-    __device__ static raw narrow(float v) { return v; }
-};
-struct F16 {
-    using raw = unsigned short;
-    __device__ static float widen(raw v) { return __half2float(__ushort_as_half(v)); }
-    __device__ static raw narrow(float v) { return __half_as_ushort(__float2half_rn(v)); }
-};
-struct BF16 {
-    using raw = unsigned short;
-    __device__ static float widen(raw v) { return __uint_as_float((unsigned)v << 16); }
-    __device__ static raw narrow(float f)   // round to nearest even, NaN stays NaN (torch's cast)
-    {
-        unsigned u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (raw)((u >> 16) | 0x40u);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (raw)(u >> 16);
-    }
-};
+// Elements are widened and narrowed with the hardware f16 conversion (load / store<DT, kHwF16>): device-only kernels.
 
 // the maps of a call: base pointers and the first concatenated channel of each (first[n] = C)
 struct MapSet {
@@ -122,10 +101,7 @@ __device__ __forceinline__ long long element_of(const Chan& ch, long long b, lon
 
 __device__ __forceinline__ long long slots_of(const Centers& ce, long long b)
 {
-    if (ce.index_form) return ce.N;
-    const long long n = ce.counts_i64 ? static_cast<const long long*>(ce.counts)[b]
-                                      : (long long)static_cast<const int*>(ce.counts)[b];
-    return n < 0 ? 0 : (n > ce.N ? ce.N : n);
+    return ce.index_form ? ce.N : clamp_count(ce.counts, b, ce.N, ce.counts_i64);
 }
 // in-plane cell of slot n (below the frame's slot count), -1 when it lies outside the map
 __device__ __forceinline__ long long cell_of(const Centers& ce, const Plane& g, long long b, long long n)
@@ -141,11 +117,11 @@ __device__ __forceinline__ long long cell_of(const Centers& ce, const Plane& g, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- gather
-template <class IO>
+template <int DT>
 __global__ __launch_bounds__(kThreads) void gather_kernel(const MapSet maps, const Centers ce, const Plane g,
-                                                          typename IO::raw* __restrict__ out)
+                                                          Stored<DT>* __restrict__ out)
 {
-    using raw = typename IO::raw;
+    using raw = Stored<DT>;
     const long long total = g.B * ce.N * g.C, stride = (long long)gridDim.x * kThreads;
     const long long plane = g.H * g.W;
     for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total; e += stride) {
@@ -162,12 +138,11 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(const MapSet maps, con
 }
 
 // ------------------------------------------------------------------------------------------------------------------ loss
-template <class IO, int KIND>
+template <int DT, int KIND>
 __global__ __launch_bounds__(kThreads) void loss_fwd_kernel(const MapSet maps, const Centers ce, const Plane g, const LossArgs la,
                                                             double* __restrict__ part_sum,
                                                             unsigned long long* __restrict__ part_cnt)
 {
-    using raw = typename IO::raw;
     const long long b = blockIdx.x, plane = g.H * g.W;
     const long long total = slots_of(ce, b) * g.C;
     double acc = 0.0;
@@ -179,24 +154,13 @@ __global__ __launch_bounds__(kThreads) void loss_fwd_kernel(const MapSet maps, c
         if (cell < 0) continue;
         cnt += c == 0;
         const Chan ch = channel_of(maps, c);
-        const float x = IO::widen(static_cast<const raw*>(ch.p)[element_of(ch, b, plane, cell)]);
+        const float x = load<DT, kHwF16>(ch.p, element_of(ch, b, plane, cell));
         const long long row = b * ce.N + n;
         const float w = la.weights ? la.weights[la.per_channel ? row * g.C + c : row] : 1.0f;
         acc += (double)(loss_of<KIND, float>(x - la.targets[row * g.C + c], la.beta) * w);
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        acc += __shfl_xor(acc, s);
-        cnt += __shfl_xor(cnt, s);
-    }
-    __shared__ double s_sum[kThreads / 64];
-    __shared__ unsigned long long s_cnt[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc, s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part_sum[b] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        part_cnt[b] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-    }
+    block_sum<double, unsigned long long, kThreads>(acc, cnt);
+    if (threadIdx.x == 0) part_sum[b] = acc, part_cnt[b] = cnt;
 }
 
 // one workgroup: the frames' partials in a fixed order -> loss, denominator
@@ -208,23 +172,10 @@ __global__ __launch_bounds__(kThreads) void loss_finish_kernel(const double* __r
     double acc = 0.0;
     unsigned long long cnt = 0;
     for (long long i = threadIdx.x; i < nparts; i += kThreads) acc += part_sum[i], cnt += part_cnt[i];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        acc += __shfl_xor(acc, s);
-        cnt += __shfl_xor(cnt, s);
-    }
-    __shared__ double s_sum[kThreads / 64];
-    __shared__ unsigned long long s_cnt[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc, s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
+    block_sum<double, unsigned long long, kThreads>(acc, cnt);
     if (threadIdx.x == 0) {
-        const double total = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        const unsigned long long valid = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-        float denom;
-        if (avg_mode == ACCV_FL_AVG_VALUE) denom = avg_value;
-        else if (avg_mode == ACCV_FL_AVG_DEVICE) denom = *avg_dev;
-        else denom = (float)(valid > 0 ? valid : 1ull);   // valid.sum().clamp(min=1), as float32
-        *out_loss = (float)(total / (double)denom);
+        const float denom = denominator(avg_mode, avg_value, avg_dev, cnt);   // valid.sum().clamp(min=1), as float32
+        *out_loss = (float)(acc / (double)denom);
         *out_denom = denom;
     }
 }
@@ -256,12 +207,12 @@ __device__ __forceinline__ void zero_span(raw* p, long long n)
 // SRC: -1 the gradient rows of gather_at_centers, otherwise the loss kind
 constexpr int kRows = -1;
 
-template <class IO, int SRC>
+template <int DT, int SRC>
 __global__ __launch_bounds__(kThreads) void scatter_kernel(const MapSet grads, const MapSet feats, const Centers ce, const Plane g,
                                                            const long long band_rows, const long long bands, const LossArgs la,
-                                                           const typename IO::raw* __restrict__ rows)
+                                                           const Stored<DT>* __restrict__ rows)
 {
-    using raw = typename IO::raw;
+    using raw = Stored<DT>;
     __shared__ int s_slot[kList], s_hit[kList];   // the frame's valid slots on cells of this band, in slot order
     __shared__ int s_wave[kThreads / 64];
     __shared__ int s_lead[kThreads];
@@ -303,7 +254,7 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const MapSet grads, c
     auto contribution = [&](long long j, int c, float x) -> float {
         const long long row = b * ce.N + j;
         if constexpr (SRC == kRows) {
-            return IO::widen(rows[row * g.C + c]);
+            return load<DT, kHwF16>(rows, row * g.C + c);
         } else {
             const float w = la.weights ? la.weights[la.per_channel ? row * g.C + c : row] : 1.0f;
             return (w * dloss_of<SRC, float>(x - la.targets[row * g.C + c], la.beta)) * scale;
@@ -321,11 +272,11 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const MapSet grads, c
             const Chan gc = channel_of(grads, c);
             const long long at = element_of(gc, b, plane, cell);
             float x = 0.0f;
-            if constexpr (SRC != kRows) x = IO::widen(static_cast<const raw*>(channel_of(feats, c).p)[at]);
+            if constexpr (SRC != kRows) x = load<DT, kHwF16>(channel_of(feats, c).p, at);
             float acc = 0.0f;
             for (int k = i; k < (int)count; ++k)
                 if (s_hit[k] == cell) acc += contribution(s_slot[k], c, x);
-            static_cast<raw*>(gc.p)[at] = IO::narrow(acc);
+            store<DT, kHwF16>(gc.p, at, acc);
         }
         return;
     }
@@ -351,11 +302,11 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const MapSet grads, c
             const Chan gc = channel_of(grads, c);
             const long long at = element_of(gc, b, plane, cell);
             float x = 0.0f;
-            if constexpr (SRC != kRows) x = IO::widen(static_cast<const raw*>(channel_of(feats, c).p)[at]);
+            if constexpr (SRC != kRows) x = load<DT, kHwF16>(channel_of(feats, c).p, at);
             float acc = 0.0f;
             for (long long j = base + i; j < ns; ++j)
                 if (cell_of(ce, g, b, j) == cell) acc += contribution(j, c, x);
-            static_cast<raw*>(gc.p)[at] = IO::narrow(acc);
+            store<DT, kHwF16>(gc.p, at, acc);
         }
     }
 }
@@ -381,7 +332,7 @@ int prepare(const char* who, const void* const* maps, const void* const* second,
         return accv::fail(ACCV_EINVAL, "%s: 1..%d maps supported, got %d", who, kMaxMaps, num_maps);
     if (!maps || !channels || (second_set && !second)) return accv::fail(ACCV_EINVAL, "%s: null array", who);
     if (H > 0 && W > 0 && H > 0x7fffffffll / W) return accv::fail(ACCV_EINVAL, "%s: a plane of %lld x %lld exceeds 2^31 - 1 cells", who, H, W);
-    pr.esize = dtype == kF32 ? 4 : 2;
+    pr.esize = (size_t)elem_size(dtype);
     pr.maps.n = num_maps;
     long long C = 0;
     for (int i = 0; i < kMaxMaps + 1; ++i) pr.maps.first[i] = 0;
@@ -437,13 +388,13 @@ void band_geometry(const Problem& pr, long long& band_rows, long long& bands)
     bands = (pr.g.H + band_rows - 1) / band_rows;
 }
 
-template <class IO>
+template <int DT>
 void launch_scatter(int src, dim3 grid, hipStream_t stream, const MapSet& grads, const MapSet& feats, const Problem& pr,
                     long long band_rows, long long bands, const LossArgs& la, const void* rows_)
 {
-    const auto* rows = static_cast<const typename IO::raw*>(rows_);
+    const auto* rows = static_cast<const Stored<DT>*>(rows_);
     const dim3 block(kThreads);
-#define SCATTER(S) hipLaunchKernelGGL((scatter_kernel<IO, S>), grid, block, 0, stream, grads, feats, pr.ce, pr.g, band_rows, bands, la, rows)
+#define SCATTER(S) hipLaunchKernelGGL((scatter_kernel<DT, S>), grid, block, 0, stream, grads, feats, pr.ce, pr.g, band_rows, bands, la, rows)
     if (src == kRows) SCATTER(kRows);
     else if (src == kL1) SCATTER(kL1);
     else SCATTER(kSmoothL1);
@@ -457,23 +408,23 @@ int scatter(const char* who, int src, int dtype, const Problem& pr, const MapSet
     if (pr.g.B == 0 || pr.g.C == 0 || pr.g.H == 0 || pr.g.W == 0) return ACCV_OK;   // the gradient maps have no elements
     long long band_rows, bands;
     band_geometry(pr, band_rows, bands);
-    if (bands > kMaxBlocks / pr.g.B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld bands exceed the grid limit", who, pr.g.B, bands);
+    if (bands > accv::kGridLimit / pr.g.B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld bands exceed the grid limit", who, pr.g.B, bands);
     const dim3 grid((unsigned)(pr.g.B * bands));
     switch (dtype) {
-        case kF32: launch_scatter<F32>(src, grid, stream, grads, pr.maps, pr, band_rows, bands, la, rows); break;
-        case kF16: launch_scatter<F16>(src, grid, stream, grads, pr.maps, pr, band_rows, bands, la, rows); break;
-        default: launch_scatter<BF16>(src, grid, stream, grads, pr.maps, pr, band_rows, bands, la, rows); break;
+        case kF32: launch_scatter<kF32>(src, grid, stream, grads, pr.maps, pr, band_rows, bands, la, rows); break;
+        case kF16: launch_scatter<kF16>(src, grid, stream, grads, pr.maps, pr, band_rows, bands, la, rows); break;
+        default: launch_scatter<kBF16>(src, grid, stream, grads, pr.maps, pr, band_rows, bands, la, rows); break;
     }
     return accv::check_launch(who);
 }
 
-template <class IO>
+template <int DT>
 void launch_loss(int kind, dim3 grid, hipStream_t stream, const Problem& pr, const LossArgs& la, double* ps, unsigned long long* pc)
 {
     if (kind == kL1)
-        hipLaunchKernelGGL((loss_fwd_kernel<IO, kL1>), grid, dim3(kThreads), 0, stream, pr.maps, pr.ce, pr.g, la, ps, pc);
+        hipLaunchKernelGGL((loss_fwd_kernel<DT, kL1>), grid, dim3(kThreads), 0, stream, pr.maps, pr.ce, pr.g, la, ps, pc);
     else
-        hipLaunchKernelGGL((loss_fwd_kernel<IO, kSmoothL1>), grid, dim3(kThreads), 0, stream, pr.maps, pr.ce, pr.g, la, ps, pc);
+        hipLaunchKernelGGL((loss_fwd_kernel<DT, kSmoothL1>), grid, dim3(kThreads), 0, stream, pr.maps, pr.ce, pr.g, la, ps, pc);
 }
 
 }  // namespace
@@ -497,9 +448,9 @@ int accv_gather_at_centers(const void* const* maps, const int* channels, int num
     blocks = blocks > 8192 ? 8192 : blocks;
     const dim3 grid((unsigned)blocks), block(kThreads);
     switch (dtype) {
-        case kF32: hipLaunchKernelGGL(gather_kernel<F32>, grid, block, 0, stream, pr.maps, pr.ce, pr.g, static_cast<float*>(out)); break;
-        case kF16: hipLaunchKernelGGL(gather_kernel<F16>, grid, block, 0, stream, pr.maps, pr.ce, pr.g, static_cast<unsigned short*>(out)); break;
-        default: hipLaunchKernelGGL(gather_kernel<BF16>, grid, block, 0, stream, pr.maps, pr.ce, pr.g, static_cast<unsigned short*>(out)); break;
+        case kF32: hipLaunchKernelGGL(gather_kernel<kF32>, grid, block, 0, stream, pr.maps, pr.ce, pr.g, static_cast<float*>(out)); break;
+        case kF16: hipLaunchKernelGGL(gather_kernel<kF16>, grid, block, 0, stream, pr.maps, pr.ce, pr.g, static_cast<uint16_t*>(out)); break;
+        default: hipLaunchKernelGGL(gather_kernel<kBF16>, grid, block, 0, stream, pr.maps, pr.ce, pr.g, static_cast<uint16_t*>(out)); break;
     }
     return accv::check_launch(who);
 }
@@ -536,23 +487,21 @@ int accv_center_regression_loss(const void* const* maps, const int* channels, in
         return rc;
     if (int rc = check_loss(who, params, true)) return rc;
     if (B == 0) return ACCV_OK;
-    if (B > kMaxBlocks) return accv::fail(ACCV_EINVAL, "%s: batch exceeds the grid limit", who);
+    if (B > accv::kGridLimit) return accv::fail(ACCV_EINVAL, "%s: batch exceeds the grid limit", who);
     if (N > 0 && pr.g.C > 0 && !targets) return accv::fail(ACCV_EINVAL, "%s: null targets pointer", who);
     if (!out_loss || !out_denom) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
     if (params->avg_mode == ACCV_FL_AVG_DEVICE && !avg_factor_dev) return accv::fail(ACCV_EINVAL, "%s: null avg_factor pointer", who);
     const size_t need = accv_center_regression_loss_workspace_bytes(B);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
-        return accv::fail(ACCV_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", who, need,
-                          workspace_bytes);
+    if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     double* ps = static_cast<double*>(workspace);
     unsigned long long* pc = reinterpret_cast<unsigned long long*>(ps + B);
     const LossArgs la{targets, weights_or_null, (flags & ACCV_CR_WEIGHTS_PER_CHANNEL) ? 1 : 0, params->beta, nullptr, nullptr};
     const dim3 grid((unsigned)B);
     switch (dtype) {
-        case kF32: launch_loss<F32>(params->kind, grid, stream, pr, la, ps, pc); break;
-        case kF16: launch_loss<F16>(params->kind, grid, stream, pr, la, ps, pc); break;
-        default: launch_loss<BF16>(params->kind, grid, stream, pr, la, ps, pc); break;
+        case kF32: launch_loss<kF32>(params->kind, grid, stream, pr, la, ps, pc); break;
+        case kF16: launch_loss<kF16>(params->kind, grid, stream, pr, la, ps, pc); break;
+        default: launch_loss<kBF16>(params->kind, grid, stream, pr, la, ps, pc); break;
     }
     if (int rc = accv::check_launch(who)) return rc;
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kThreads), 0, stream, ps, pc, B, params->avg_mode, params->avg_factor,

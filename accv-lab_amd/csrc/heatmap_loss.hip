@@ -16,15 +16,16 @@
 // 1 - sigmoid(x) is computed from exp(-|x|) directly (not as 1 - p in f32), so log(1 - p) and the sigmoid derivative keep
 // their relative precision where the sigmoid saturates; the clamp tests compare that accurate value against eps.
 #include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
 
 #include <cstdint>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 
 namespace {
 
-enum DType { kF32 = 0, kF16 = 1, kBF16 = 2 };   // the codes of accv_matched_pair_reduce (f64 is not taken here)
+using namespace accv;   // dtype codes (f64 is not taken here), decode / encode, block_sum, denominator
+
 constexpr int kThreads = 256;
 constexpr long long kMaxBlocks = 2048;          // 8 workgroups per CU: the forward grid and the workspace slots
 constexpr float kLogEps = 1e-12f;
@@ -32,67 +33,6 @@ constexpr float kLogEps = 1e-12f;
 struct FocalParams {
     float alpha, gamma, pos_weight, neg_weight, clamp_eps;
 };
-
-// 16 bytes of logits per lane: VEC elements
-template <class T>
-struct Logits;
-template <>
-struct Logits<float> {
-    static constexpr int VEC = 4;
-    __device__ static void load(const void* p, long long c, float (&x)[VEC])
-    {
-        const float4 v = static_cast<const float4*>(p)[c];
-        x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
-    }
-    __device__ static float one(const void* p, long long i) { return static_cast<const float*>(p)[i]; }
-    __device__ static void store(void* p, long long c, const float (&g)[VEC])
-    {
-        static_cast<float4*>(p)[c] = make_float4(g[0], g[1], g[2], g[3]);
-    }
-    __device__ static void store_one(void* p, long long i, float g) { static_cast<float*>(p)[i] = g; }
-};
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f)   // round to nearest even, NaN stays NaN (torch's cast)
-{
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ float f16_to_f32(unsigned short h) { return __half2float(__ushort_as_half(h)); }
-__device__ __forceinline__ unsigned short f32_to_f16(float f) { return __half_as_ushort(__float2half_rn(f)); }
-
-template <bool BF16>
-struct HalfLogits {
-    static constexpr int VEC = 8;
-    __device__ static float cvt(unsigned short h) { return BF16 ? bf16_to_f32(h) : f16_to_f32(h); }
-    __device__ static unsigned short back(float f) { return BF16 ? f32_to_bf16(f) : f32_to_f16(f); }
-    __device__ static void load(const void* p, long long c, float (&x)[VEC])
-    {
-        const uint4 v = static_cast<const uint4*>(p)[c];
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            x[2 * k] = cvt((unsigned short)(w[k] & 0xffffu));
-            x[2 * k + 1] = cvt((unsigned short)(w[k] >> 16));
-        }
-    }
-    __device__ static float one(const void* p, long long i) { return cvt(static_cast<const unsigned short*>(p)[i]); }
-    __device__ static void store(void* p, long long c, const float (&g)[VEC])
-    {
-        unsigned w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = (unsigned)back(g[2 * k]) | ((unsigned)back(g[2 * k + 1]) << 16);
-        static_cast<uint4*>(p)[c] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    __device__ static void store_one(void* p, long long i, float g) { static_cast<unsigned short*>(p)[i] = back(g); }
-};
-template <>
-struct Logits<__half> : HalfLogits<false> {};
-struct bf16_tag {};
-template <>
-struct Logits<bf16_tag> : HalfLogits<true> {};
 
 template <int VEC>
 __device__ __forceinline__ void load_target(const float* __restrict__ t, long long c, float (&y)[VEC])
@@ -199,14 +139,13 @@ long long fwd_blocks(long long numel)
     return b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b);
 }
 
-template <class T, bool INT_POW>
+template <int DT, bool INT_POW>
 __global__ __launch_bounds__(kThreads) void focal_fwd_kernel(const void* __restrict__ logits, const float* __restrict__ target,
                                                              long long numel, int vec_ok, FocalParams f,
                                                              double* __restrict__ part_sum,
                                                              unsigned long long* __restrict__ part_pos)
 {
-    using L = Logits<T>;
-    constexpr int VEC = L::VEC;
+    constexpr int VEC = 16 / elem_size(DT);   // 16 bytes of logits per lane, widened to f32 (hardware f16 conversion)
     double acc = 0.0;
     unsigned npos = 0;
     const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
@@ -223,40 +162,29 @@ __global__ __launch_bounds__(kThreads) void focal_fwd_kernel(const void* __restr
     long long c = tid;
     for (; c + stride < nchunks; c += 2 * stride) {   // two chunks in flight per lane
         float x0[VEC], y0[VEC], x1[VEC], y1[VEC];
-        L::load(logits, c, x0);
+        decode<DT, kHwF16>(static_cast<const uint4*>(logits)[c], x0);
         load_target<VEC>(target, c, y0);
-        L::load(logits, c + stride, x1);
+        decode<DT, kHwF16>(static_cast<const uint4*>(logits)[c + stride], x1);
         load_target<VEC>(target, c + stride, y1);
         chunk(x0, y0);
         chunk(x1, y1);
     }
     if (c < nchunks) {
         float x0[VEC], y0[VEC];
-        L::load(logits, c, x0);
+        decode<DT, kHwF16>(static_cast<const uint4*>(logits)[c], x0);
         load_target<VEC>(target, c, y0);
         chunk(x0, y0);
     }
     // the tail (and every element when the pointers are not 16-byte aligned), one element per lane
     for (long long i = nchunks * VEC + tid; i < numel; i += stride) {
         const float y = target[i];
-        acc += (double)focal_value<INT_POW>(L::one(logits, i), y, f);
+        acc += (double)focal_value<INT_POW>(load<DT, kHwF16>(logits, i), y, f);
         npos += y == 1.0f;
     }
 
     unsigned long long cnt = npos;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        acc += __shfl_xor(acc, s);
-        cnt += __shfl_xor(cnt, s);
-    }
-    __shared__ double s_sum[kThreads / 64];
-    __shared__ unsigned long long s_cnt[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc, s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part_sum[blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        part_pos[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-    }
+    block_sum<double, unsigned long long, kThreads>(acc, cnt);
+    if (threadIdx.x == 0) part_sum[blockIdx.x] = acc, part_pos[blockIdx.x] = cnt;
 }
 
 // one workgroup: the block slots in a fixed order -> loss, denominator
@@ -268,35 +196,21 @@ __global__ __launch_bounds__(kThreads) void focal_finish_kernel(const double* __
     double acc = 0.0;
     unsigned long long cnt = 0;
     for (int i = threadIdx.x; i < nparts; i += kThreads) acc += part_sum[i], cnt += part_pos[i];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        acc += __shfl_xor(acc, s);
-        cnt += __shfl_xor(cnt, s);
-    }
-    __shared__ double s_sum[kThreads / 64];
-    __shared__ unsigned long long s_cnt[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc, s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
+    block_sum<double, unsigned long long, kThreads>(acc, cnt);
     if (threadIdx.x == 0) {
-        const double total = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        const unsigned long long npos = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-        float denom;
-        if (avg_mode == ACCV_FL_AVG_VALUE) denom = avg_value;
-        else if (avg_mode == ACCV_FL_AVG_DEVICE) denom = *avg_dev;
-        else denom = (float)(npos > 0 ? npos : 1ull);   // pos.sum().clamp(min=1), as float32
-        *out_loss = (float)(total / (double)denom);
+        const float denom = denominator(avg_mode, avg_value, avg_dev, cnt);   // pos.sum().clamp(min=1), as float32
+        *out_loss = (float)(acc / (double)denom);
         *out_denom = denom;
     }
 }
 
-template <class T, bool INT_POW>
+template <int DT, bool INT_POW>
 __global__ __launch_bounds__(kThreads) void focal_bwd_kernel(const void* __restrict__ logits, const float* __restrict__ target,
                                                              long long numel, int vec_ok, FocalParams f,
                                                              const float* __restrict__ grad_out,
                                                              const float* __restrict__ denom, void* __restrict__ grad)
 {
-    using L = Logits<T>;
-    constexpr int VEC = L::VEC;
+    constexpr int VEC = 16 / elem_size(DT);   // 16 bytes of logits per lane, widened to f32 (hardware f16 conversion)
     const float scale = *grad_out / *denom;
     const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
     const long long nchunks = vec_ok ? numel / VEC : 0;
@@ -304,26 +218,26 @@ __global__ __launch_bounds__(kThreads) void focal_bwd_kernel(const void* __restr
         float g[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) g[k] = scale * focal_grad<INT_POW>(x[k], y[k], f);
-        L::store(grad, cc, g);
+        static_cast<uint4*>(grad)[cc] = encode<DT, kHwF16>(g);
     };
     long long c = tid;
     for (; c + stride < nchunks; c += 2 * stride) {
         float x0[VEC], y0[VEC], x1[VEC], y1[VEC];
-        L::load(logits, c, x0);
+        decode<DT, kHwF16>(static_cast<const uint4*>(logits)[c], x0);
         load_target<VEC>(target, c, y0);
-        L::load(logits, c + stride, x1);
+        decode<DT, kHwF16>(static_cast<const uint4*>(logits)[c + stride], x1);
         load_target<VEC>(target, c + stride, y1);
         chunk(c, x0, y0);
         chunk(c + stride, x1, y1);
     }
     if (c < nchunks) {
         float x0[VEC], y0[VEC];
-        L::load(logits, c, x0);
+        decode<DT, kHwF16>(static_cast<const uint4*>(logits)[c], x0);
         load_target<VEC>(target, c, y0);
         chunk(c, x0, y0);
     }
     for (long long i = nchunks * VEC + tid; i < numel; i += stride)
-        L::store_one(grad, i, scale * focal_grad<INT_POW>(L::one(logits, i), target[i], f));
+        store<DT, kHwF16>(grad, i, scale * focal_grad<INT_POW>(load<DT, kHwF16>(logits, i), target[i], f));
 }
 
 int check_args(const char* who, const void* logits, const void* target, long long numel, int dtype, const FocalParams& f)
@@ -349,20 +263,20 @@ int vectors_ok(const void* logits, const void* target, const void* grad = nullpt
 
 bool int_pow(const FocalParams& f) { return f.alpha == 2.0f && f.gamma == 4.0f; }
 
-template <class T>
+template <int DT>
 void launch_fwd(bool ip, dim3 grid, hipStream_t stream, const void* x, const float* t, long long n, int vec, const FocalParams& f,
                 double* ps, unsigned long long* pp)
 {
-    if (ip) hipLaunchKernelGGL((focal_fwd_kernel<T, true>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, ps, pp);
-    else hipLaunchKernelGGL((focal_fwd_kernel<T, false>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, ps, pp);
+    if (ip) hipLaunchKernelGGL((focal_fwd_kernel<DT, true>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, ps, pp);
+    else hipLaunchKernelGGL((focal_fwd_kernel<DT, false>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, ps, pp);
 }
 
-template <class T>
+template <int DT>
 void launch_bwd(bool ip, dim3 grid, hipStream_t stream, const void* x, const float* t, long long n, int vec, const FocalParams& f,
                 const float* go, const float* den, void* g)
 {
-    if (ip) hipLaunchKernelGGL((focal_bwd_kernel<T, true>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, go, den, g);
-    else hipLaunchKernelGGL((focal_bwd_kernel<T, false>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, go, den, g);
+    if (ip) hipLaunchKernelGGL((focal_bwd_kernel<DT, true>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, go, den, g);
+    else hipLaunchKernelGGL((focal_bwd_kernel<DT, false>), grid, dim3(kThreads), 0, stream, x, t, n, vec, f, go, den, g);
 }
 
 }  // namespace
@@ -389,9 +303,7 @@ int accv_gaussian_focal_loss(const void* logits, const float* target, long long 
     if (!out_loss || !out_denom) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
     if (avg_mode == ACCV_FL_AVG_DEVICE && !avg_factor_dev) return accv::fail(ACCV_EINVAL, "%s: null avg_factor pointer", who);
     const size_t need = accv_gaussian_focal_loss_workspace_bytes(numel);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
-        return accv::fail(ACCV_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", who, need,
-                          workspace_bytes);
+    if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const long long blocks = fwd_blocks(numel);
     double* ps = static_cast<double*>(workspace);
@@ -400,9 +312,9 @@ int accv_gaussian_focal_loss(const void* logits, const float* target, long long 
     const dim3 grid((unsigned)blocks);
     const bool ip = int_pow(f);
     switch (dtype) {
-        case kF32: launch_fwd<float>(ip, grid, stream, logits, target, numel, vec, f, ps, pp); break;
-        case kF16: launch_fwd<__half>(ip, grid, stream, logits, target, numel, vec, f, ps, pp); break;
-        default: launch_fwd<bf16_tag>(ip, grid, stream, logits, target, numel, vec, f, ps, pp); break;
+        case kF32: launch_fwd<kF32>(ip, grid, stream, logits, target, numel, vec, f, ps, pp); break;
+        case kF16: launch_fwd<kF16>(ip, grid, stream, logits, target, numel, vec, f, ps, pp); break;
+        default: launch_fwd<kBF16>(ip, grid, stream, logits, target, numel, vec, f, ps, pp); break;
     }
     if (int rc = accv::check_launch(who)) return rc;
     hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(kThreads), 0, stream, ps, pp, (int)blocks, avg_mode, avg_factor,
@@ -421,15 +333,15 @@ int accv_gaussian_focal_loss_bwd(const void* logits, const float* target, long l
     if (!grad_out || !denom || !grad_logits) return accv::fail(ACCV_EINVAL, "%s: null grad_out / denom / gradient pointer", who);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int vec = vectors_ok(logits, target, grad_logits);
-    const long long per_block = (long long)kThreads * (dtype == kF32 ? 4 : 8) * 2;   // two vectors per lane per pass
+    const long long per_block = (long long)kThreads * (16 / elem_size(dtype)) * 2;   // two vectors per lane per pass
     long long blocks = (numel + per_block - 1) / per_block;
     blocks = blocks > 4 * kMaxBlocks ? 4 * kMaxBlocks : blocks;
     const dim3 grid((unsigned)blocks);
     const bool ip = int_pow(f);
     switch (dtype) {
-        case kF32: launch_bwd<float>(ip, grid, stream, logits, target, numel, vec, f, grad_out, denom, grad_logits); break;
-        case kF16: launch_bwd<__half>(ip, grid, stream, logits, target, numel, vec, f, grad_out, denom, grad_logits); break;
-        default: launch_bwd<bf16_tag>(ip, grid, stream, logits, target, numel, vec, f, grad_out, denom, grad_logits); break;
+        case kF32: launch_bwd<kF32>(ip, grid, stream, logits, target, numel, vec, f, grad_out, denom, grad_logits); break;
+        case kF16: launch_bwd<kF16>(ip, grid, stream, logits, target, numel, vec, f, grad_out, denom, grad_logits); break;
+        default: launch_bwd<kBF16>(ip, grid, stream, logits, target, numel, vec, f, grad_out, denom, grad_logits); break;
     }
     return accv::check_launch(who);
 }

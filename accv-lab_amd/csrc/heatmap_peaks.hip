@@ -26,15 +26,16 @@
 // bitonic network and writes scores, indices, classes, ys and xs.  The LDS slot counters only place the winners before the
 // sort; output order comes from the unique keys alone, so results are bitwise reproducible.  Bandwidth work: no MFMA.
 #include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
 
 #include <cstdint>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 
 namespace {
 
-enum DType { kF32 = 0, kF16 = 1, kBF16 = 2 };   // the codes of accv_gaussian_focal_loss
+using namespace accv;   // dtype codes (f64 is not taken here), load / store<DT> with the hardware f16 conversion
+
 constexpr int kThreads = 256;
 constexpr int kPerThread = 16;
 constexpr int kChunk = kThreads * kPerThread;   // interior elements of one chunk: 4096
@@ -77,14 +78,6 @@ struct Params {
     int per_class;
     long long chunks_per_group;
 };
-
-template <int DT>
-__device__ __forceinline__ float load_one(const void* __restrict__ p, long long i)
-{
-    if constexpr (DT == kF32) return static_cast<const float*>(p)[i];
-    else if constexpr (DT == kF16) return __half2float(static_cast<const __half*>(p)[i]);
-    else return __uint_as_float((unsigned)static_cast<const unsigned short*>(p)[i] << 16);
-}
 
 // max_pool2d's window maximum: a NaN anywhere in the window makes it NaN (fmaxf would skip it).  One v_maximum3_f32
 // per two elements on gfx950, as v_max3_f32 for fmaxf.
@@ -210,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void peaks_chunk_kernel(const void* __res
 #pragma unroll
             for (int d = -HALF; d <= HALF; ++d) {
                 const bool ok = e < na && row + d >= 0 && row + d < p.H;
-                v[u][d + HALF] = ok ? load_one<DT>(x, base + d * p.W) : -INFINITY;
+                v[u][d + HALF] = ok ? load<DT, kHwF16>(x, base + d * p.W) : -INFINITY;
             }
         }
 #pragma unroll
@@ -327,9 +320,9 @@ __global__ __launch_bounds__(kGroupThreads) void peaks_group_kernel(const u64* _
         const long long in_plane = p.per_class ? idx : idx - cls * hw;
         const long long o = g * k + i;
         const float s = score_of(key);
-        if (dtype == kF32) static_cast<float*>(scores)[o] = s;
-        else if (dtype == kF16) static_cast<__half*>(scores)[o] = __float2half_rn(s);   // exact: s came from an f16
-        else static_cast<unsigned short*>(scores)[o] = (unsigned short)(__float_as_uint(s) >> 16);   // exact, as above
+        if (dtype == kF32) store<kF32>(scores, o, s);
+        else if (dtype == kF16) store<kF16, kHwF16>(scores, o, s);   // exact: s came from an f16
+        else static_cast<uint16_t*>(scores)[o] = (uint16_t)(__float_as_uint(s) >> 16);   // exact, as above: truncation is enough
         indices[o] = in_plane;
         classes[o] = cls;
         ys[o] = in_plane / p.W;
@@ -354,9 +347,9 @@ int check_args(const char* who, long long B, long long C, long long H, long long
 long long chunk_blocks(long long B, long long C, long long H, long long W)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
-    if (H > kMaxGroup / W || B > 0x7fffffffll || C > 0x7fffffffll / B) return -1;
+    if (H > kMaxGroup / W || B > accv::kGridLimit || C > accv::kGridLimit / B) return -1;
     const long long pp = geometry(H, W).per_plane();
-    if (pp > 0x7fffffffll / (B * C)) return -1;
+    if (pp > accv::kGridLimit / (B * C)) return -1;
     return B * C * pp;
 }
 
@@ -404,9 +397,7 @@ int accv_heatmap_peaks(const void* x, int dtype, long long B, long long C, long 
     if (!x) return accv::fail(ACCV_EINVAL, "%s: null heat-map pointer", who);
     if (!scores || !indices || !classes || !ys || !xs) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
     const size_t need = accv_heatmap_peaks_workspace_bytes(B, C, H, W, k);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
-        return accv::fail(ACCV_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", who, need,
-                          workspace_bytes);
+    if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     const Geometry g = geometry(H, W);
     Params p;
     p.H = H, p.W = W, p.C = C;

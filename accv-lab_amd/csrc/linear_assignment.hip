@@ -28,18 +28,19 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <limits>
 #include <mutex>
 #include <vector>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-enum DType { kF32 = 0, kF16 = 1, kBF16 = 2, kF64 = 3 };
+using namespace accv;   // dtype codes, load<DT>, clamp_count
+
 constexpr long long kMaxLarge = 4096;   // max(R, C)
 constexpr long long kMaxSmall = 1024;   // min(R, C)
 constexpr int kAssignedTag = 4096;      // tag bit of an assigned column (> every column index)
@@ -63,39 +64,13 @@ struct Args {
     int M, N;      // LDS capacity: max(R, C), min(R, C)
 };
 
-__host__ __device__ inline long long clamp_count(const long long* counts, long long b, long long cap)
-{
-    if (!counts) return cap;
-    const long long v = counts[b];
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
-__host__ __device__ inline float half_bits_to_float(uint16_t h)
-{
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    const uint32_t e = (h >> 10) & 0x1fu, f = h & 0x3ffu;
-    if (e == 0) {   // zero / subnormal: f * 2^-24 is exact in f32
-        const float mag = (float)f * 5.9604644775390625e-8f;
-        return sign ? -mag : mag;
-    }
-    uint32_t bits = e == 31 ? (sign | 0x7f800000u | (f << 13)) : (sign | ((e + 112u) << 23) | (f << 13));
-    float out;
-    memcpy(&out, &bits, 4);
-    return out;
-}
-
 __host__ __device__ inline double load_cost(const void* p, int dtype, long long off)
 {
     switch (dtype) {
-        case kF32: return (double)static_cast<const float*>(p)[off];
-        case kF64: return static_cast<const double*>(p)[off];
-        case kF16: return (double)half_bits_to_float(static_cast<const uint16_t*>(p)[off]);
-        default: {
-            const uint32_t bits = (uint32_t)static_cast<const uint16_t*>(p)[off] << 16;
-            float out;
-            memcpy(&out, &bits, 4);
-            return (double)out;
-        }
+        case kF32: return (double)load<kF32>(p, off);
+        case kF64: return load<kF64>(p, off);
+        case kF16: return (double)load<kF16>(p, off);   // software f16, as the host solver
+        default: return (double)load<kBF16>(p, off);
     }
 }
 
@@ -369,9 +344,8 @@ int accv_linear_assignment(const void* cost, int dtype, long long B, long long R
     if (int rc = check_args(who, cost, dtype, B, R, C, flags, row_ind, col_ind, sizes, status)) return rc;
     if (B == 0) return ACCV_OK;
     const size_t need = accv_linear_assignment_workspace_bytes(B, R, C, dtype);
-    if (need > 0 && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u)))
-        return accv::fail(ACCV_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", who, need,
-                          workspace_bytes);
+    if (need > 0)
+        if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     Args a;
     a.cost = cost, a.R = R, a.C = C, a.sb = stride_b, a.sr = stride_r, a.sc = stride_c;
     a.rows = row_counts, a.cols = col_counts, a.maximize = (flags & ACCV_LSA_MAXIMIZE) ? 1 : 0;

@@ -37,7 +37,6 @@ constexpr int kThreads = 256;
 constexpr int kFinishThreads = 1024;
 constexpr int kMaxQ = 1024;                 // queries per workgroup the LDS tables hold
 constexpr long long kTargetElems = 8192;    // elements per workgroup aimed at
-constexpr long long kMaxBlocks = 0x7fffffffll;
 constexpr unsigned kKnownFlags = ACCV_MF_IDX_I64 | ACCV_MF_LABELS_I64;
 constexpr int kNoSlot = INT_MAX;
 
@@ -54,19 +53,6 @@ struct Args {
     long long nqb;              // workgroups per frame
 };
 
-// vector width in elements of a 16-byte access
-template <int DT> struct Vec { static constexpr int n = DT == kF32 ? 4 : (DT == kF64 ? 2 : 8); };
-template <int DT> struct ESize { static constexpr int n = DT == kF32 ? 4 : (DT == kF64 ? 8 : 2); };
-
-__host__ __device__ inline long long clamp_count(const long long* counts, long long b, long long cap)
-{
-    const long long v = counts[b];
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
-__host__ __device__ inline long long load_index(const void* p, long long i, int is64)
-{
-    return is64 ? static_cast<const long long*>(p)[i] : (long long)static_cast<const int*>(p)[i];
-}
 // label of the pair in slot j of frame b as a table entry: the class, or -1 for background
 __host__ __device__ inline int label_of_slot(const Args& a, long long b, int j)
 {
@@ -94,9 +80,9 @@ __device__ __forceinline__ void build_table(const Args& a, long long b, long lon
     const int tid = threadIdx.x;
     for (int i = tid; i < nq; i += kThreads) s_lab[i] = kNoSlot;
     __syncthreads();
-    const long long n = clamp_count(a.counts, b, a.K);
+    const long long n = clamp_count(a.counts, b, a.K, 1);
     for (long long j = tid; j < n; j += kThreads) {
-        long long q, g;
+        long long q, g;   // both indices in ONE branch on their dtype, so the two loads are in flight together
         if (a.idx64) {
             q = static_cast<const long long*>(a.pind)[b * a.K + j];
             g = static_cast<const long long*>(a.gind)[b * a.K + j];
@@ -132,49 +118,6 @@ __device__ __forceinline__ void walk(unsigned e0, unsigned n, unsigned C, Fn&& f
     }
 }
 
-template <int DT>
-__device__ __forceinline__ void decode(const uint4& v, typename Compute<DT>::type (&x)[Vec<DT>::n])
-{
-    if constexpr (DT == kF32) {
-        x[0] = __uint_as_float(v.x), x[1] = __uint_as_float(v.y), x[2] = __uint_as_float(v.z), x[3] = __uint_as_float(v.w);
-    } else if constexpr (DT == kF64) {
-        x[0] = __hiloint2double((int)v.y, (int)v.x), x[1] = __hiloint2double((int)v.w, (int)v.z);
-    } else {
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if constexpr (DT == kF16) {
-                x[2 * k] = accv_mc::half_bits_to_float((uint16_t)(w[k] & 0xffffu));
-                x[2 * k + 1] = accv_mc::half_bits_to_float((uint16_t)(w[k] >> 16));
-            } else {
-                x[2 * k] = __uint_as_float(w[k] << 16);
-                x[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-            }
-        }
-    }
-}
-
-template <int DT>
-__device__ __forceinline__ uint4 encode(const typename Compute<DT>::type (&g)[Vec<DT>::n])
-{
-    if constexpr (DT == kF32) {
-        return make_uint4(__float_as_uint(g[0]), __float_as_uint(g[1]), __float_as_uint(g[2]), __float_as_uint(g[3]));
-    } else if constexpr (DT == kF64) {
-        return make_uint4((unsigned)__double2loint(g[0]), (unsigned)__double2hiint(g[0]), (unsigned)__double2loint(g[1]),
-                          (unsigned)__double2hiint(g[1]));
-    } else {
-        unsigned w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if constexpr (DT == kF16)
-                w[k] = (unsigned)float_to_half_bits(g[2 * k]) | ((unsigned)float_to_half_bits(g[2 * k + 1]) << 16);
-            else
-                w[k] = (unsigned)float_to_bf16_bits(g[2 * k]) | ((unsigned)float_to_bf16_bits(g[2 * k + 1]) << 16);
-        }
-        return make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
 // the range of a workgroup: frame, first query, number of queries, elements
 struct Range {
     long long b, q0;
@@ -195,7 +138,7 @@ __device__ __forceinline__ Range range_of(const Args& a)
 template <int DT>
 __device__ __forceinline__ unsigned head_of(uintptr_t addr, unsigned total)
 {
-    const unsigned h = (unsigned)((16u - (unsigned)(addr & 15u)) & 15u) / ESize<DT>::n;
+    const unsigned h = (unsigned)((16u - (unsigned)(addr & 15u)) & 15u) / elem_size(DT);
     return h < total ? h : total;
 }
 
@@ -204,10 +147,9 @@ __global__ __launch_bounds__(kThreads) void mf_fwd_kernel(const Args a, const Co
                                                           double* __restrict__ part)
 {
     using F = typename Compute<DT>::type;
-    constexpr int V = Vec<DT>::n;
+    constexpr int V = 16 / elem_size(DT);   // elements of a 16-byte access
     __shared__ int s_lab[kMaxQ];
     __shared__ F s_w[kMaxQ];
-    __shared__ double s_sum[kThreads / 64];
     const Range r = range_of(a);
     build_table<DT>(a, r.b, r.q0, r.nq, s_lab, s_w);
     const unsigned C = (unsigned)a.C;
@@ -215,11 +157,11 @@ __global__ __launch_bounds__(kThreads) void mf_fwd_kernel(const Args a, const Co
     double acc = 0.0;
     auto one = [&](F x, unsigned q, unsigned c) { acc += (double)(s_w[q] * focal_value<F, G2>(x, (int)c == s_lab[q], k)); };
     if (a.sq == a.C) {
-        const char* base = static_cast<const char*>(a.x) + first * ESize<DT>::n;
+        const char* base = static_cast<const char*>(a.x) + first * elem_size(DT);
         const unsigned head = head_of<DT>(reinterpret_cast<uintptr_t>(base), r.total);
         const unsigned nvec = (r.total - head) / V, tail0 = head + nvec * V;
         walk<V>(head, nvec, C, [&](unsigned i, unsigned q, unsigned c) {
-            const uint4 v = *reinterpret_cast<const uint4*>(base + ((size_t)head + (size_t)i * V) * ESize<DT>::n);
+            const uint4 v = *reinterpret_cast<const uint4*>(base + ((size_t)head + (size_t)i * V) * elem_size(DT));
             F x[V];
             decode<DT>(v, x);
 #pragma unroll
@@ -235,14 +177,13 @@ __global__ __launch_bounds__(kThreads) void mf_fwd_kernel(const Args a, const Co
     } else {
         walk<1>(0u, r.total, C, [&](unsigned, unsigned q, unsigned c) { one(load<DT>(a.x, first + (long long)q * a.sq + c), q, c); });
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+    acc = block_sum<double, kThreads>(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
-// one workgroup, a wave per frame: the frame's partials in a fixed order, the number of pairs, the denominator
+// one workgroup, a wave per frame: the frame's partials in a fixed order, the number of pairs, the denominator.
+// Not block_sum: 1024 threads whose 16 wave counts are added one after the other (integers, any order gives the same
+// count), and per-frame sums that stay inside one wave.  Both butterflies keep their own order.
 template <class O>
 __global__ __launch_bounds__(kFinishThreads) void mf_finish_kernel(const double* __restrict__ part,
                                                                    const long long* __restrict__ counts, long long B,
@@ -255,7 +196,7 @@ __global__ __launch_bounds__(kFinishThreads) void mf_finish_kernel(const double*
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned long long m = 0;
     if (avg_mode == ACCV_FL_AVG_NUM_POS)
-        for (long long b = threadIdx.x; b < B; b += kFinishThreads) m += (unsigned long long)clamp_count(counts, b, K);
+        for (long long b = threadIdx.x; b < B; b += kFinishThreads) m += (unsigned long long)clamp_count(counts, b, K, 1);
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) m += __shfl_xor(m, s);
     if (lane == 0) s_cnt[wave] = m;
@@ -263,10 +204,7 @@ __global__ __launch_bounds__(kFinishThreads) void mf_finish_kernel(const double*
     if (threadIdx.x == 0) {
         unsigned long long total = 0;
         for (int i = 0; i < kFinishThreads / 64; ++i) total += s_cnt[i];
-        double denom;
-        if (avg_mode == ACCV_FL_AVG_VALUE) denom = avg_value;
-        else if (avg_mode == ACCV_FL_AVG_DEVICE) denom = (double)*avg_dev;
-        else denom = (double)(total > 0 ? total : 1ull);
+        const double denom = denominator(avg_mode, avg_value, avg_dev, total);
         s_denom = denom;
         *out_denom = denom;
     }
@@ -287,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
                                                           void* __restrict__ grad)
 {
     using F = typename Compute<DT>::type;
-    constexpr int V = Vec<DT>::n;
+    constexpr int V = 16 / elem_size(DT);   // elements of a 16-byte access
     __shared__ int s_lab[kMaxQ];
     __shared__ F s_w[kMaxQ];
     const Range r = range_of(a);
@@ -297,14 +235,14 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
     const long long gfirst = (r.b * a.Q + r.q0) * a.C;   // the gradient is contiguous
     const F scale = (F)((double)grad_out[r.b] / *denom);
     auto one = [&](F x, unsigned q, unsigned c) -> F { return (s_w[q] * focal_grad<F, G2>(x, (int)c == s_lab[q], k)) * scale; };
-    const char* base = static_cast<const char*>(a.x) + first * ESize<DT>::n;
-    char* gbase = static_cast<char*>(grad) + gfirst * ESize<DT>::n;
+    const char* base = static_cast<const char*>(a.x) + first * elem_size(DT);
+    char* gbase = static_cast<char*>(grad) + gfirst * elem_size(DT);
     const bool same = ((reinterpret_cast<uintptr_t>(base) ^ reinterpret_cast<uintptr_t>(gbase)) & 15u) == 0;
     if (a.sq == a.C && same) {
         const unsigned head = head_of<DT>(reinterpret_cast<uintptr_t>(base), r.total);
         const unsigned nvec = (r.total - head) / V, tail0 = head + nvec * V;
         walk<V>(head, nvec, C, [&](unsigned i, unsigned q, unsigned c) {
-            const size_t at = ((size_t)head + (size_t)i * V) * ESize<DT>::n;
+            const size_t at = ((size_t)head + (size_t)i * V) * elem_size(DT);
             const uint4 v = *reinterpret_cast<const uint4*>(base + at);
             F x[V], g[V];
             decode<DT>(v, x);
@@ -331,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
 void host_table(const Args& a, long long b, std::vector<int>& tab)
 {
     tab.assign((size_t)a.Q, kNoSlot);
-    const long long n = clamp_count(a.counts, b, a.K);
+    const long long n = clamp_count(a.counts, b, a.K, 1);
     for (long long j = 0; j < n; ++j) {
         const long long q = load_index(a.pind, b * a.K + j, a.idx64), g = load_index(a.gind, b * a.K + j, a.idx64);
         if (q >= 0 && q < a.Q && g >= 0 && g < a.G && tab[(size_t)q] == kNoSlot) tab[(size_t)q] = (int)j;
@@ -341,11 +279,10 @@ void host_table(const Args& a, long long b, std::vector<int>& tab)
 
 double host_denom(const Args& a, int avg_mode, double avg_value, const float* avg_ptr)
 {
-    if (avg_mode == ACCV_FL_AVG_VALUE) return avg_value;
-    if (avg_mode == ACCV_FL_AVG_DEVICE) return (double)*avg_ptr;
     unsigned long long m = 0;
-    for (long long b = 0; b < a.B; ++b) m += (unsigned long long)clamp_count(a.counts, b, a.K);
-    return (double)(m > 0 ? m : 1ull);
+    if (avg_mode == ACCV_FL_AVG_NUM_POS)
+        for (long long b = 0; b < a.B; ++b) m += (unsigned long long)clamp_count(a.counts, b, a.K, 1);
+    return denominator(avg_mode, avg_value, avg_ptr, m);
 }
 
 template <int DT, bool G2, class O>
@@ -412,15 +349,14 @@ int check_args(const char* who, const void* logits, const void* labels, const vo
     if (!logits || !counts) return accv::fail(ACCV_EINVAL, "%s: null logits / counts pointer", who);
     if (K > 0 && (!pind || !gind)) return accv::fail(ACCV_EINVAL, "%s: null index pointer", who);
     if (K > 0 && G > 0 && !labels) return accv::fail(ACCV_EINVAL, "%s: null labels pointer", who);
-    const uintptr_t esize = dtype == kF32 ? 4 : (dtype == kF64 ? 8 : 2);
-    if (reinterpret_cast<uintptr_t>(logits) % esize) return accv::fail(ACCV_EINVAL, "%s: logits are not aligned to their element size", who);
+    if (reinterpret_cast<uintptr_t>(logits) % (uintptr_t)elem_size(dtype)) return accv::fail(ACCV_EINVAL, "%s: logits are not aligned to their element size", who);
     if (forward && p->avg_mode == ACCV_FL_AVG_DEVICE && !p->avg_factor_dev)
         return accv::fail(ACCV_EINVAL, "%s: null avg_factor pointer", who);
     a.x = logits, a.labels = labels, a.pind = pind, a.gind = gind, a.counts = counts, a.w = nullptr;
     a.B = B, a.Q = Q, a.C = C, a.G = G, a.K = K, a.sb = sb, a.sq = sq;
     a.idx64 = (flags & ACCV_MF_IDX_I64) ? 1 : 0, a.lab64 = (flags & ACCV_MF_LABELS_I64) ? 1 : 0;
     geometry(Q, C, a.qpb, a.nqb);
-    if (a.nqb > kMaxBlocks / B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld workgroups exceed the grid limit", who, B, a.nqb);
+    if (a.nqb > accv::kGridLimit / B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld workgroups exceed the grid limit", who, B, a.nqb);
     return ACCV_OK;
 }
 
@@ -475,7 +411,7 @@ size_t accv_matched_focal_loss_workspace_bytes(long long B, long long Q, long lo
     int qpb;
     long long nqb;
     geometry(Q, C, qpb, nqb);
-    if (nqb > kMaxBlocks / B) return 0;
+    if (nqb > accv::kGridLimit / B) return 0;
     return accv::align_up((size_t)(B * nqb) * sizeof(double), 16);
 }
 
@@ -495,9 +431,7 @@ int accv_matched_focal_loss(const void* logits, const void* gt_labels, const voi
     a.w = query_weights_or_null;
     if (!out || !out_denom) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
     const size_t need = accv_matched_focal_loss_workspace_bytes(B, Q, C);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
-        return accv::fail(ACCV_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", who, need,
-                          workspace_bytes);
+    if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
     switch (dtype) {
@@ -524,7 +458,7 @@ int accv_matched_focal_loss_bwd(const void* logits, const void* gt_labels, const
     if (empty) return ACCV_OK;
     a.w = query_weights_or_null;
     if (!grad_out || !denom || !grad_logits) return accv::fail(ACCV_EINVAL, "%s: null grad_out / denom / gradient pointer", who);
-    if (reinterpret_cast<uintptr_t>(grad_logits) % (dtype == kF32 ? 4u : (dtype == kF64 ? 8u : 2u)))
+    if (reinterpret_cast<uintptr_t>(grad_logits) % (uintptr_t)elem_size(dtype))
         return accv::fail(ACCV_EINVAL, "%s: the gradient is not aligned to its element size", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {

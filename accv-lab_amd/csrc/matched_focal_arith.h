@@ -20,69 +20,14 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
-#include "matching_cost_arith.h"   // DType codes, Compute<DT>, load<DT>, m_exp / m_pow / m_abs
+#include "accv_numeric.h"
 
 #pragma clang fp contract(off)
 
 namespace accv_mf {
 
-using accv_mc::Compute;
-using accv_mc::kBF16;
-using accv_mc::kF16;
-using accv_mc::kF32;
-using accv_mc::kF64;
-using accv_mc::load;
-using accv_mc::m_abs;
-using accv_mc::m_exp;
-using accv_mc::m_pow;
-
-__host__ __device__ inline float m_log1p(float x) { return log1pf(x); }
-__host__ __device__ inline double m_log1p(double x) { return log1p(x); }
-
-// float -> f16 bits, round to nearest even (torch's cast); NaN stays NaN
-__host__ __device__ inline uint16_t float_to_half_bits(float f)
-{
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
-    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);   // 65520 and above round to infinity
-    if (x < 0x38800000u) {   // below 2^-14: a subnormal half (or zero): f * 2^24 rounded to an integer by the 2^23 trick
-        float a;
-        memcpy(&a, &x, 4);
-        a = a * 16777216.0f;
-        a = a + 8388608.0f;
-        uint32_t r;
-        memcpy(&r, &a, 4);
-        return (uint16_t)(sign | (r - 0x4b000000u));
-    }
-    const uint32_t odd = (x >> 13) & 1u;
-    x += 0xfffu + odd;
-    return (uint16_t)(sign | ((x >> 13) - (112u << 10)));
-}
-
-// float -> bf16 bits, round to nearest even, NaN stays NaN (torch's cast)
-__host__ __device__ inline uint16_t float_to_bf16_bits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// v narrowed to dtype DT at element `off`
-template <int DT>
-__host__ __device__ inline void store(void* p, long long off, typename Compute<DT>::type v)
-{
-    if constexpr (DT == kF32) static_cast<float*>(p)[off] = v;
-    else if constexpr (DT == kF64) static_cast<double*>(p)[off] = v;
-    else if constexpr (DT == kF16) static_cast<uint16_t*>(p)[off] = float_to_half_bits(v);
-    else static_cast<uint16_t*>(p)[off] = float_to_bf16_bits(v);
-}
+using namespace accv;   // dtype codes, Compute<DT>, load / store<DT> (software f16: the host twin runs the same code), m_*
 
 template <class F>
 struct Coef {

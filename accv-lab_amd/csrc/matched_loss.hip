@@ -11,11 +11,11 @@
 // with float atomics into zero-initialised gradients (matches are one-to-one in practice, duplicates stay correct).
 // Memory / launch bound (a few hundred KB per call): no MFMA, no roofline claim beyond "one launch instead of ~12".
 #include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
 
 #include <cstdint>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 #include "pointwise_loss_arith.h"
 
 namespace {
@@ -26,30 +26,11 @@ namespace {
 //   kOneHotL1  (:37-43 class branch + :225-238) a holds integer class labels [B, w_a], b the scores [B, w_b, C]:
 //              sum_c |onehot(label)[c] - score[c]|
 using namespace accv_loss;   // Kind and the element-wise loss_of / dloss_of (pointwise_loss_arith.h)
-enum DType { kF32 = 0, kF16 = 1, kBF16 = 2, kF64 = 3 };
-struct bf16_raw {
-    uint16_t v;
-};
+using namespace accv;        // dtype codes, Compute<DT> (f32 arithmetic for f32, f16 and bf16 data as in the gathers this kernel
+                             // replaces, batched_indexing_access_cuda_impl.cu:269-286; f64 for f64), load<DT>, load_index, block_sum
 
-// arithmetic / accumulation type: float for f32, f16 and bf16 data (the gathers this kernel replaces accept them,
-// batched_indexing_access_cuda_impl.cu:269-286), double for f64
-template <class T>
-struct AccOf {
-    using type = float;
-};
-template <>
-struct AccOf<double> {
-    using type = double;
-};
-__device__ __forceinline__ float to_acc(float v) { return v; }
-__device__ __forceinline__ double to_acc(double v) { return v; }
-__device__ __forceinline__ float to_acc(__half v) { return __half2float(v); }
-__device__ __forceinline__ float to_acc(bf16_raw v) { return __uint_as_float((unsigned)v.v << 16); }
+// elements are widened with the hardware f16 conversion (load<DT, kHwF16>): device-only kernels
 
-__device__ __forceinline__ long long load_int(const void* p, long long i, int is64)
-{
-    return is64 ? static_cast<const long long*>(p)[i] : (long long)static_cast<const int*>(p)[i];
-}
 __device__ __forceinline__ void load_int_pair(const void* p, const void* q, long long i, int is64, long long& a, long long& b)
 {
     if (is64) {
@@ -113,88 +94,71 @@ struct MatchedDesc {
     float beta, eps;
 };
 
-// wave shuffle + LDS tree in a FIXED order: deterministic
-template <class A>
-__device__ __forceinline__ void block_sum_store(A acc, A* __restrict__ out, long long i)
+template <int KIND, int DT>
+__global__ __launch_bounds__(256) void matched_reduce_kernel(const MatchedDesc d, typename Compute<DT>::type* __restrict__ out)
 {
-    __shared__ A s_part[4];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[i] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-}
-
-template <int KIND, class T>
-__global__ __launch_bounds__(256) void matched_reduce_kernel(const MatchedDesc d, typename AccOf<T>::type* __restrict__ out)
-{
-    using A = typename AccOf<T>::type;
-    const T* __restrict__ da = static_cast<const T*>(d.a);
-    const T* __restrict__ db = static_cast<const T*>(d.b);
-    const T* __restrict__ dw = static_cast<const T*>(d.weights);
+    using A = typename Compute<DT>::type;
     const long long i = blockIdx.x;
-    const long long n = max(0ll, min(load_int(d.counts, i, d.counts_i64), d.w_idx));
+    const long long n = max(0ll, min(load_index(d.counts, i, d.counts_i64), d.w_idx));   // = clamp_count; this spelling keeps the compiled kernels as they were
     const long long work = KIND == kIoUxyxy ? 1 : d.row;   // work items per pair
     const long long total = n * work;
     A acc = A(0);
     for (long long t = threadIdx.x; t < total; t += 256) {
         const long long j = t / work, k = t - j * work;
-        long long ia, ib;   // both match indices in ONE branch on their dtype: two load_int() calls are two branch diamonds, and
+        long long ia, ib;   // both match indices in ONE branch on their dtype: two load_index() calls are two branch diamonds, and
                             // hipcc waits for the first index before it requests the second (a dependent round trip for nothing)
         load_int_pair(d.idx_a, d.idx_b, i * d.idx_stride + j, d.idx_i64, ia, ib);
         const long long ga = wrap_index(ia, d.w_a), gb = wrap_index(ib, d.w_b);
         if (ga < 0 || gb < 0) continue;
-        const A w = dw ? to_acc(dw[i * d.w_a + ga]) : A(1);
+        const A w = d.weights ? load<DT, kHwF16>(d.weights, i * d.w_a + ga) : A(1);
         if constexpr (KIND == kIoUxyxy) {
             A ba[4], bb[4], ga_[4], gb_[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                ba[c] = to_acc(da[(i * d.w_a + ga) * 4 + c]);
-                bb[c] = to_acc(db[(i * d.w_b + gb) * 4 + c]);
+                ba[c] = load<DT, kHwF16>(d.a, (i * d.w_a + ga) * 4 + c);
+                bb[c] = load<DT, kHwF16>(d.b, (i * d.w_b + gb) * 4 + c);
             }
             acc += w * iou_loss<A, false>(ba, bb, (A)d.eps, ga_, gb_);
         } else if constexpr (KIND == kOneHotL1) {
-            const long long label = load_int(d.a, i * d.w_a + ga, d.labels_i64);
+            const long long label = load_index(d.a, i * d.w_a + ga, d.labels_i64);
             const A target = (k == label) ? A(1) : A(0);
-            acc += w * loss_of<KIND, A>(target - to_acc(db[(i * d.w_b + gb) * d.row + k]), A(0));
+            acc += w * loss_of<KIND, A>(target - load<DT, kHwF16>(d.b, (i * d.w_b + gb) * d.row + k), A(0));
         } else {
-            const A diff = to_acc(da[(i * d.w_a + ga) * d.row + k]) - to_acc(db[(i * d.w_b + gb) * d.row + k]);
+            const A diff = load<DT, kHwF16>(d.a, (i * d.w_a + ga) * d.row + k) - load<DT, kHwF16>(d.b, (i * d.w_b + gb) * d.row + k);
             acc += w * loss_of<KIND, A>(diff, (A)d.beta);
         }
     }
-    block_sum_store<A>(acc, out, i);
+    acc = block_sum<A, 256>(acc);   // wave shuffle + LDS tree in a FIXED order: deterministic
+    if (threadIdx.x == 0) out[i] = acc;
 }
 
-template <int KIND, class T>
+template <int KIND, int DT>
 __global__ __launch_bounds__(256) void matched_reduce_bwd_kernel(const MatchedDesc d,
-                                                                 const typename AccOf<T>::type* __restrict__ grad_out,
-                                                                 typename AccOf<T>::type* __restrict__ grad_a,
-                                                                 typename AccOf<T>::type* __restrict__ grad_b,
-                                                                 typename AccOf<T>::type* __restrict__ grad_w)
+                                                                 const typename Compute<DT>::type* __restrict__ grad_out,
+                                                                 typename Compute<DT>::type* __restrict__ grad_a,
+                                                                 typename Compute<DT>::type* __restrict__ grad_b,
+                                                                 typename Compute<DT>::type* __restrict__ grad_w)
 {
-    using A = typename AccOf<T>::type;
-    const T* __restrict__ da = static_cast<const T*>(d.a);
-    const T* __restrict__ db = static_cast<const T*>(d.b);
-    const T* __restrict__ dw = static_cast<const T*>(d.weights);
+    using A = typename Compute<DT>::type;
     const long long i = blockIdx.x;
-    const long long n = max(0ll, min(load_int(d.counts, i, d.counts_i64), d.w_idx));
+    const long long n = max(0ll, min(load_index(d.counts, i, d.counts_i64), d.w_idx));   // = clamp_count; this spelling keeps the compiled kernels as they were
     const long long work = KIND == kIoUxyxy ? 1 : d.row;
     const long long total = n * work;
     const A g = grad_out[i];
     for (long long t = threadIdx.x; t < total; t += 256) {
         const long long j = t / work, k = t - j * work;
-        long long ia, ib;   // both match indices in ONE branch on their dtype: two load_int() calls are two branch diamonds, and
+        long long ia, ib;   // both match indices in ONE branch on their dtype: two load_index() calls are two branch diamonds, and
                             // hipcc waits for the first index before it requests the second (a dependent round trip for nothing)
         load_int_pair(d.idx_a, d.idx_b, i * d.idx_stride + j, d.idx_i64, ia, ib);
         const long long ga = wrap_index(ia, d.w_a), gb = wrap_index(ib, d.w_b);
         if (ga < 0 || gb < 0) continue;
-        const A w = dw ? to_acc(dw[i * d.w_a + ga]) : A(1);
+        const A w = d.weights ? load<DT, kHwF16>(d.weights, i * d.w_a + ga) : A(1);
         if constexpr (KIND == kIoUxyxy) {
             A ba[4], bb[4], ga_[4], gb_[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                ba[c] = to_acc(da[(i * d.w_a + ga) * 4 + c]);
-                bb[c] = to_acc(db[(i * d.w_b + gb) * 4 + c]);
+                ba[c] = load<DT, kHwF16>(d.a, (i * d.w_a + ga) * 4 + c);
+                bb[c] = load<DT, kHwF16>(d.b, (i * d.w_b + gb) * 4 + c);
             }
             const A l = iou_loss<A, true>(ba, bb, (A)d.eps, ga_, gb_);
 #pragma unroll
@@ -204,14 +168,14 @@ __global__ __launch_bounds__(256) void matched_reduce_bwd_kernel(const MatchedDe
             }
             if (grad_w) atomicAdd(grad_w + i * d.w_a + ga, g * l);
         } else if constexpr (KIND == kOneHotL1) {
-            const long long label = load_int(d.a, i * d.w_a + ga, d.labels_i64);
+            const long long label = load_index(d.a, i * d.w_a + ga, d.labels_i64);
             const long long eb = (i * d.w_b + gb) * d.row + k;
-            const A diff = ((k == label) ? A(1) : A(0)) - to_acc(db[eb]);
+            const A diff = ((k == label) ? A(1) : A(0)) - load<DT, kHwF16>(d.b, eb);
             if (grad_b) atomicAdd(grad_b + eb, -g * w * dloss_of<KIND, A>(diff, A(0)));
             if (grad_w) atomicAdd(grad_w + i * d.w_a + ga, g * loss_of<KIND, A>(diff, A(0)));
         } else {
             const long long ea = (i * d.w_a + ga) * d.row + k, eb = (i * d.w_b + gb) * d.row + k;
-            const A diff = to_acc(da[ea]) - to_acc(db[eb]);
+            const A diff = load<DT, kHwF16>(d.a, ea) - load<DT, kHwF16>(d.b, eb);
             const A dl = g * w * dloss_of<KIND, A>(diff, (A)d.beta);
             if (grad_a) atomicAdd(grad_a + ea, dl);
             if (grad_b) atomicAdd(grad_b + eb, -dl);
@@ -228,32 +192,32 @@ int check(const char* who, const MatchedDesc& d, long long batch, int kind, int 
     if (dtype < 0 || dtype > kF64) return accv::fail(ACCV_EINVAL, "%s: unknown data type code %d", who, dtype);
     if (kind == kSmoothL1 && !(d.beta > 0.0f)) return accv::fail(ACCV_EINVAL, "%s: smooth-L1 needs beta > 0", who);
     if (kind == kIoUxyxy && d.row != 4) return accv::fail(ACCV_EINVAL, "%s: the IoU loss needs rows of 4 (x0, y0, x1, y1)", who);
-    if (batch > 0x7fffffffll) return accv::fail(ACCV_EINVAL, "%s: batch exceeds the grid limit", who);
+    if (batch > accv::kGridLimit) return accv::fail(ACCV_EINVAL, "%s: batch exceeds the grid limit", who);
     return ACCV_OK;
 }
 
-template <class T>
+template <int DT>
 void launch_fwd(int kind, const dim3& grid, hipStream_t stream, const MatchedDesc& d, void* out_)
 {
-    auto* out = static_cast<typename AccOf<T>::type*>(out_);
+    auto* out = static_cast<typename Compute<DT>::type*>(out_);
     const dim3 block(256);
     switch (kind) {
-        case kL1: hipLaunchKernelGGL((matched_reduce_kernel<kL1, T>), grid, block, 0, stream, d, out); break;
-        case kL2: hipLaunchKernelGGL((matched_reduce_kernel<kL2, T>), grid, block, 0, stream, d, out); break;
-        case kSmoothL1: hipLaunchKernelGGL((matched_reduce_kernel<kSmoothL1, T>), grid, block, 0, stream, d, out); break;
-        case kIoUxyxy: hipLaunchKernelGGL((matched_reduce_kernel<kIoUxyxy, T>), grid, block, 0, stream, d, out); break;
-        default: hipLaunchKernelGGL((matched_reduce_kernel<kOneHotL1, T>), grid, block, 0, stream, d, out); break;
+        case kL1: hipLaunchKernelGGL((matched_reduce_kernel<kL1, DT>), grid, block, 0, stream, d, out); break;
+        case kL2: hipLaunchKernelGGL((matched_reduce_kernel<kL2, DT>), grid, block, 0, stream, d, out); break;
+        case kSmoothL1: hipLaunchKernelGGL((matched_reduce_kernel<kSmoothL1, DT>), grid, block, 0, stream, d, out); break;
+        case kIoUxyxy: hipLaunchKernelGGL((matched_reduce_kernel<kIoUxyxy, DT>), grid, block, 0, stream, d, out); break;
+        default: hipLaunchKernelGGL((matched_reduce_kernel<kOneHotL1, DT>), grid, block, 0, stream, d, out); break;
     }
 }
-template <class T>
+template <int DT>
 void launch_bwd(int kind, const dim3& grid, hipStream_t stream, const MatchedDesc& d, const void* go_, void* ga_, void* gb_,
                 void* gw_)
 {
-    using A = typename AccOf<T>::type;
+    using A = typename Compute<DT>::type;
     const A* go = static_cast<const A*>(go_);
     A *ga = static_cast<A*>(ga_), *gb = static_cast<A*>(gb_), *gw = static_cast<A*>(gw_);
     const dim3 block(256);
-#define BWD(K) hipLaunchKernelGGL((matched_reduce_bwd_kernel<K, T>), grid, block, 0, stream, d, go, ga, gb, gw)
+#define BWD(K) hipLaunchKernelGGL((matched_reduce_bwd_kernel<K, DT>), grid, block, 0, stream, d, go, ga, gb, gw)
     switch (kind) {
         case kL1: BWD(kL1); break;
         case kL2: BWD(kL2); break;
@@ -284,10 +248,10 @@ int accv_matched_pair_reduce(const void* a, const void* b, const void* idx_a, co
         return accv::fail(ACCV_EINVAL, "matched_pair_reduce: null data / index pointer");
     const dim3 grid((unsigned)batch);
     switch (dtype) {
-        case kF32: launch_fwd<float>(kind, grid, stream, d, out); break;
-        case kF16: launch_fwd<__half>(kind, grid, stream, d, out); break;
-        case kBF16: launch_fwd<bf16_raw>(kind, grid, stream, d, out); break;
-        default: launch_fwd<double>(kind, grid, stream, d, out); break;
+        case kF32: launch_fwd<kF32>(kind, grid, stream, d, out); break;
+        case kF16: launch_fwd<kF16>(kind, grid, stream, d, out); break;
+        case kBF16: launch_fwd<kBF16>(kind, grid, stream, d, out); break;
+        default: launch_fwd<kF64>(kind, grid, stream, d, out); break;
     }
     return accv::check_launch("matched_pair_reduce");
 }
@@ -312,10 +276,10 @@ int accv_matched_pair_reduce_bwd(const void* a, const void* b, const void* idx_a
         return accv::fail(ACCV_EINVAL, "matched_pair_reduce_bwd: integer labels have no gradient");
     const dim3 grid((unsigned)batch);
     switch (dtype) {
-        case kF32: launch_bwd<float>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
-        case kF16: launch_bwd<__half>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
-        case kBF16: launch_bwd<bf16_raw>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
-        default: launch_bwd<double>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
+        case kF32: launch_bwd<kF32>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
+        case kF16: launch_bwd<kF16>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
+        case kBF16: launch_bwd<kBF16>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
+        default: launch_bwd<kF64>(kind, grid, stream, d, grad_out, grad_a_or_null, grad_b_or_null, grad_w_or_null); break;
     }
     return accv::check_launch("matched_pair_reduce_bwd");
 }

@@ -27,13 +27,6 @@ constexpr int kThreads = 256;
 constexpr int kRowsPerLane = 8;   // queries per lane and workgroup
 constexpr unsigned kKnownFlags = ACCV_MC_LABELS_I64 | ACCV_MC_CXCYWH;
 
-__host__ __device__ inline long long clamp_count(const long long* counts, long long b, long long cap)
-{
-    if (!counts) return cap;
-    const long long v = counts[b];
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
 struct Args {
     const void* scores;
     const void* pboxes;
@@ -63,7 +56,7 @@ __host__ __device__ inline void load_column(const Args& a, const Params<typename
     c.label = 0, c.label_ok = false;
     if (p.cls) {
         const long long off = b * a.G + g;
-        c.label = L64 ? static_cast<const long long*>(a.labels)[off] : (long long)static_cast<const int*>(a.labels)[off];
+        c.label = load_index(a.labels, off, L64);
         c.label_ok = c.label >= 0 && c.label < a.C;
     }
 #pragma unroll

@@ -17,59 +17,17 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstring>
+
+#include "accv_numeric.h"
 
 #pragma clang fp contract(off)
 
 namespace accv_mc {
 
-enum DType { kF32 = 0, kF16 = 1, kBF16 = 2, kF64 = 3 };
+using namespace accv;   // dtype codes, Compute<DT>, load<DT> (software f16: the host twin runs the same code), m_*
+
 enum Kind { kOneMinusProb = 0, kNegProb = 1, kFocal = 2 };
 constexpr int kMaxD = 16;
-
-template <int DT> struct Compute { using type = float; };
-template <> struct Compute<kF64> { using type = double; };
-
-__host__ __device__ inline float half_bits_to_float(uint16_t h)
-{
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    const uint32_t e = (h >> 10) & 0x1fu, f = h & 0x3ffu;
-    if (e == 0) {   // zero / subnormal: f * 2^-24 is exact in f32
-        const float mag = (float)f * 5.9604644775390625e-8f;
-        return sign ? -mag : mag;
-    }
-    uint32_t bits = e == 31 ? (sign | 0x7f800000u | (f << 13)) : (sign | ((e + 112u) << 23) | (f << 13));
-    float out;
-    memcpy(&out, &bits, 4);
-    return out;
-}
-
-// element `off` of a float tensor of dtype DT, widened exactly to the compute type
-template <int DT>
-__host__ __device__ inline typename Compute<DT>::type load(const void* p, long long off)
-{
-    if constexpr (DT == kF32) {
-        return static_cast<const float*>(p)[off];
-    } else if constexpr (DT == kF64) {
-        return static_cast<const double*>(p)[off];
-    } else if constexpr (DT == kF16) {
-        return half_bits_to_float(static_cast<const uint16_t*>(p)[off]);
-    } else {
-        const uint32_t bits = (uint32_t)static_cast<const uint16_t*>(p)[off] << 16;
-        float out;
-        memcpy(&out, &bits, 4);
-        return out;
-    }
-}
-
-__host__ __device__ inline float m_exp(float x) { return expf(x); }
-__host__ __device__ inline double m_exp(double x) { return exp(x); }
-__host__ __device__ inline float m_log(float x) { return logf(x); }
-__host__ __device__ inline double m_log(double x) { return log(x); }
-__host__ __device__ inline float m_pow(float x, float y) { return powf(x, y); }
-__host__ __device__ inline double m_pow(double x, double y) { return pow(x, y); }
-__host__ __device__ inline float m_abs(float x) { return fabsf(x); }
-__host__ __device__ inline double m_abs(double x) { return fabs(x); }
 
 // NaN-keeping max / min / floor (torch.maximum / torch.minimum / clamp semantics for NaN)
 template <class F> __host__ __device__ inline F max_nan(F a, F b) { return a < b ? b : (b != b ? b : a); }

@@ -27,6 +27,7 @@
 #include <limits>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 #include "polyline_arith.h"
 
 namespace {
@@ -36,6 +37,7 @@ constexpr int kLdsBudgetBytes = 48 * 1024;
 constexpr int kWidePoints = 2048;     // polylines of at least this many points take 1024-thread workgroups
 constexpr int kSpreadGroups = 512;    // launches of at most this many single-pass workgroups give each thread one query
 
+// the dtype codes of the polyline entry points: ABI, and not the order of accv::DType
 enum PolyType { kPF32 = 0, kPF64 = 1, kPF16 = 2, kPBF16 = 3 };
 
 template <int TY>
@@ -72,13 +74,8 @@ template <>
 struct Storage<kPBF16> {
     using T = uint16_t;
     using Acc = float;
-    static __device__ __forceinline__ Acc load(const T* p) { return __uint_as_float((uint32_t)(*p) << 16); }
-    static __device__ __forceinline__ void store(T* p, Acc v)
-    {
-        uint32_t u = __float_as_uint(v);
-        *p = ((u & 0x7fffffffu) > 0x7f800000u) ? (uint16_t)((u >> 16) | 0x40u)
-                                               : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
+    static __device__ __forceinline__ Acc load(const T* p) { return accv::bf16_bits_to_float(*p); }
+    static __device__ __forceinline__ void store(T* p, Acc v) { *p = accv::float_to_bf16_bits(v); }
     static __device__ __forceinline__ void copy(T* d, const T* s) { *d = *s; }
 };
 
@@ -96,11 +93,6 @@ struct PolyParams {
     int counts_i64, relative, use_scratch;
     int q_chunk;            // queries per workgroup: blockIdx.y walks the chunks of one polyline (multiple of kThreads)
 };
-
-__device__ __forceinline__ long long load_count(const void* p, long long i, int is64)
-{
-    return is64 ? static_cast<const long long*>(p)[i] : (long long)static_cast<const int*>(p)[i];
-}
 
 // accum[i] = distance from the first point to point i (accum[0] = 0), for the n points of one polyline, by the whole
 // workgroup: segment lengths by contiguous per-thread chunks, the THREADS chunk totals scanned by wave 0.  Shared by the
@@ -203,8 +195,8 @@ __global__ __launch_bounds__(THREADS) void polyline_kernel(const PolyParams p)
     const long long b = blockIdx.x;
     const int t = threadIdx.x;
     int n = p.P, q = p.Q;
-    if (p.point_counts) n = (int)max(0ll, min((long long)p.P, load_count(p.point_counts, b, p.counts_i64)));
-    if (p.dist_counts) q = (int)max(0ll, min((long long)p.Q, load_count(p.dist_counts, b, p.counts_i64)));
+    if (p.point_counts) n = (int)max(0ll, min((long long)p.P, accv::load_index(p.point_counts, b, p.counts_i64)));
+    if (p.dist_counts) q = (int)max(0ll, min((long long)p.Q, accv::load_index(p.dist_counts, b, p.counts_i64)));
     const T* pts = static_cast<const T*>(p.points) + (size_t)b * p.P * D;
     T* out = p.out_points ? static_cast<T*>(p.out_points) + (size_t)b * p.Q * D : nullptr;
     const Acc nan = std::numeric_limits<Acc>::quiet_NaN();
@@ -546,8 +538,8 @@ __global__ __launch_bounds__(THREADS) void polyline_grad_kernel(const GradParams
     const int c = (int)blockIdx.y;
     const int t = threadIdx.x;
     int n = p.P, q = p.Q;
-    if (p.point_counts) n = (int)max(0ll, min((long long)p.P, load_count(p.point_counts, b, p.counts_i64)));
-    if (p.dist_counts) q = (int)max(0ll, min((long long)p.Q, load_count(p.dist_counts, b, p.counts_i64)));
+    if (p.point_counts) n = (int)max(0ll, min((long long)p.P, accv::load_index(p.point_counts, b, p.counts_i64)));
+    if (p.dist_counts) q = (int)max(0ll, min((long long)p.Q, accv::load_index(p.dist_counts, b, p.counts_i64)));
     const T* pts = static_cast<const T*>(p.points) + (size_t)b * p.P * D;
     const size_t row = (size_t)p.P * D;
     T* gpts = p.grad_points && p.chunks == 1 ? static_cast<T*>(p.grad_points) + (size_t)b * row : nullptr;
@@ -954,9 +946,7 @@ void sample_host(const void* points, const void* distances, const void* pc, cons
                  long long batch, int P, int Q, int D, int counts_i64, int relative, int threads)
 {
     auto count_of = [&](const void* c, long long i, int cap) {
-        if (!c) return cap;
-        const long long v = counts_i64 ? static_cast<const long long*>(c)[i] : (long long)static_cast<const int*>(c)[i];
-        return (int)std::max(0ll, std::min(v, (long long)cap));
+        return c ? (int)accv::clamp_count(c, i, cap, counts_i64) : cap;
     };
     auto run = [&](long long lo, long long hi) {
         std::vector<double> acc;
@@ -1062,9 +1052,7 @@ void grad_host(const void* points, const void* distances, const void* pc, const 
                int counts_i64, int relative, int threads)
 {
     auto count_of = [&](const void* c, long long i, int cap) {
-        if (!c) return cap;
-        const long long v = counts_i64 ? static_cast<const long long*>(c)[i] : (long long)static_cast<const int*>(c)[i];
-        return (int)std::max(0ll, std::min(v, (long long)cap));
+        return c ? (int)accv::clamp_count(c, i, cap, counts_i64) : cap;
     };
     auto run = [&](long long lo, long long hi) {
         std::vector<double> acc, gacc, bs;

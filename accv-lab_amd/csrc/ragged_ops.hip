@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "accv_common.h"
+#include "accv_numeric.h"
 
 namespace {
 
@@ -59,10 +60,7 @@ struct RaggedDesc {
     int* err;  // optional out-of-range counter
 };
 
-__device__ __forceinline__ long long load_int(const void* p, long long i, int is64)
-{
-    return is64 ? static_cast<const long long*>(p)[i] : (long long)static_cast<const int*>(p)[i];
-}
+using accv::load_index;
 
 // negative indices wrap once (reference :75-77); returns -1 when out of range
 __device__ __forceinline__ long long wrap_index(long long j, long long width, int* err)
@@ -107,9 +105,9 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const RaggedDesc d, cons
         // the count (uniform: scalar load) and the index of this slot are fetched together; slots behind the count hold
         // anything (the reference fills them with out-of-range junk) and are never interpreted
         const long long slot = i * d.idx_stride + j;
-        const long long a = load_int(d.idx_a, slot, d.idx_i64);
-        const long long b = MODE == kMapPairs ? load_int(d.idx_b, slot, d.idx_i64) : 0;
-        if (j >= load_int(d.counts, i, d.counts_i64)) continue;
+        const long long a = load_index(d.idx_a, slot, d.idx_i64);
+        const long long b = MODE == kMapPairs ? load_index(d.idx_b, slot, d.idx_i64) : 0;
+        if (j >= load_index(d.counts, i, d.counts_i64)) continue;
         long long from, to;
         if (MODE == kGather) {
             const long long s = wrap_index(a, d.w_src, d.err);
@@ -145,9 +143,9 @@ __global__ __launch_bounds__(256) void gather_fill_kernel(const RaggedDesc d, co
     int v0, lanes;
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
-        const long long a = load_int(d.idx_a, i * d.idx_stride + j, d.idx_i64);
+        const long long a = load_index(d.idx_a, i * d.idx_stride + j, d.idx_i64);
         long long s = -1;
-        if (j < load_int(d.counts, i, d.counts_i64)) s = wrap_index(a, d.w_src, d.err);
+        if (j < load_index(d.counts, i, d.counts_i64)) s = wrap_index(a, d.w_src, d.err);
         const long long from = (i * d.w_src + max(s, 0ll)) * d.row_vecs, to = (i * d.w_idx + j) * d.row_vecs;
         for (long long v = v0; v < d.row_vecs; v += lanes) dst[to + v] = s >= 0 ? src[from + v] : pattern;
     }
@@ -164,8 +162,8 @@ __global__ __launch_bounds__(256) void insert_const_kernel(const RaggedDesc d, c
     int v0, lanes;
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
-        const long long a = load_int(d.idx_a, i * d.idx_stride + j, d.idx_i64);
-        if (j >= load_int(d.counts, i, d.counts_i64)) continue;
+        const long long a = load_index(d.idx_a, i * d.idx_stride + j, d.idx_i64);
+        if (j >= load_index(d.counts, i, d.counts_i64)) continue;
         const long long o = wrap_index(a, d.w_dst, d.err);
         if (o < 0) continue;
         const long long to = (i * d.w_dst + o) * d.row_vecs;
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(256) void pad_fill_kernel(void* __restrict__ data_,
     V* data = static_cast<V*>(data_);
     const long long step = (long long)gridDim.x * 256;
     for (long long i = blockIdx.y; i < batch; i += gridDim.y) {
-        const long long c = min(max(load_int(counts, i, counts_i64), 0ll), width);
+        const long long c = min(max(load_index(counts, i, counts_i64), 0ll), width);
         const long long end = (i + 1) * width * row_vecs;
         for (long long v = (i * width + c) * row_vecs + (long long)blockIdx.x * 256 + threadIdx.x; v < end; v += step)
             data[v] = pattern;
@@ -196,32 +194,19 @@ __global__ __launch_bounds__(256) void pad_fill_kernel(void* __restrict__ data_,
 // ---- accumulate: dst[i, out(i,j), k] += src[i, in(i,j), k]
 enum AccType { kF32 = 0, kF64 = 1, kI32 = 2, kI64 = 3, kF16 = 4, kBF16 = 5 };
 
-__device__ __forceinline__ float half_bits_to_float(uint16_t h) { return (float)(*reinterpret_cast<const _Float16*>(&h)); }
-__device__ __forceinline__ uint16_t float_to_half_bits(float f)
-{
-    _Float16 h = (_Float16)f;
-    return *reinterpret_cast<uint16_t*>(&h);
-}
-__device__ __forceinline__ float bf16_bits_to_float(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
-__device__ __forceinline__ uint16_t float_to_bf16_bits(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);  // keep NaN a NaN
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
+// f16 / bf16 sums: widen, add in f32, narrow (hardware f16 conversion: device-only kernel)
 template <bool BF>
 __device__ __forceinline__ void atomic_add_16(uint16_t* addr, uint16_t val_bits)
 {
     uint32_t* word = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(addr) & ~(uintptr_t)3);
     const bool hi = (reinterpret_cast<uintptr_t>(addr) & 2) != 0;
-    const float add = BF ? bf16_bits_to_float(val_bits) : half_bits_to_float(val_bits);
+    const float add = BF ? accv::bf16_bits_to_float(val_bits) : accv::half_bits_to_float<accv::kHwF16>(val_bits);
     uint32_t old = *word, assumed;
     do {
         assumed = old;
         const uint16_t cur = hi ? (uint16_t)(assumed >> 16) : (uint16_t)(assumed & 0xffffu);
-        const float sum = (BF ? bf16_bits_to_float(cur) : half_bits_to_float(cur)) + add;
-        const uint16_t nb = BF ? float_to_bf16_bits(sum) : float_to_half_bits(sum);
+        const float sum = (BF ? accv::bf16_bits_to_float(cur) : accv::half_bits_to_float<accv::kHwF16>(cur)) + add;
+        const uint16_t nb = BF ? accv::float_to_bf16_bits(sum) : accv::float_to_half_bits<accv::kHwF16>(sum);
         const uint32_t repl = hi ? ((assumed & 0x0000ffffu) | ((uint32_t)nb << 16)) : ((assumed & 0xffff0000u) | nb);
         old = atomicCAS(word, assumed, repl);
     } while (old != assumed);
@@ -236,9 +221,9 @@ __global__ __launch_bounds__(256) void accumulate_rows_kernel(const RaggedDesc d
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;   // row_vecs == elements per row here
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
         const long long slot = i * d.idx_stride + j;
-        const long long a = load_int(d.idx_a, slot, d.idx_i64);
-        const long long b = pairs ? load_int(d.idx_b, slot, d.idx_i64) : 0;
-        if (j >= load_int(d.counts, i, d.counts_i64)) continue;
+        const long long a = load_index(d.idx_a, slot, d.idx_i64);
+        const long long b = pairs ? load_index(d.idx_b, slot, d.idx_i64) : 0;
+        if (j >= load_index(d.counts, i, d.counts_i64)) continue;
         long long s_row, o;
         if (pairs) {
             const long long s = wrap_index(a, d.w_src, d.err);
@@ -279,7 +264,7 @@ __global__ __launch_bounds__(256) void mask_to_indices_kernel(const uint8_t* __r
     const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= batch) return;
     long long limit = width;
-    if (valid) limit = max(0ll, min(width, load_int(valid, row, valid_i64)));
+    if (valid) limit = max(0ll, min(width, load_index(valid, row, valid_i64)));
     const uint8_t* m = mask + row * width;
     long long* o = out_idx + row * width;
     long long offset = 0;
@@ -327,7 +312,7 @@ __global__ __launch_bounds__(256) void mask_seg_count_kernel(const uint8_t* __re
     __shared__ int s_w[4];
     const long long row = blockIdx.y;
     long long limit = width;
-    if (valid) limit = max(0ll, min(width, load_int(valid, row, valid_i64)));
+    if (valid) limit = max(0ll, min(width, load_index(valid, row, valid_i64)));
     const long long j0 = (long long)blockIdx.x * kSeg + (long long)threadIdx.x * 16;
     int c = j0 < limit ? __popc(nonzero_bytes16(mask + row * width, j0, limit, vec != 0)) : 0;
 #pragma unroll
@@ -347,7 +332,7 @@ __global__ __launch_bounds__(256) void mask_seg_write_kernel(const uint8_t* __re
     const long long row = blockIdx.y;
     const int seg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     long long limit = width;
-    if (valid) limit = max(0ll, min(width, load_int(valid, row, valid_i64)));
+    if (valid) limit = max(0ll, min(width, load_index(valid, row, valid_i64)));
     if (wave == 0) {  // offsets of this row's segments: hits before this one, and the row total
         long long before = 0, total = 0;
         for (int s0 = 0; s0 < segs; s0 += 64) {
@@ -414,7 +399,7 @@ __global__ __launch_bounds__(256) void mask_seg_onepass_kernel(const uint8_t* __
     const long long row = blockIdx.y;
     const int seg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     long long limit = width;
-    if (valid) limit = max(0ll, min(width, load_int(valid, row, valid_i64)));
+    if (valid) limit = max(0ll, min(width, load_index(valid, row, valid_i64)));
     const uint8_t* mrow = mask + row * width;
     unsigned bits = 0;
     int before = 0, total = 0;
@@ -478,7 +463,7 @@ __global__ __launch_bounds__(NW * 64) void mask_to_indices_block_kernel(const ui
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long row = blockIdx.x;
     long long limit = width;
-    if (valid) limit = max(0ll, min(width, load_int(valid, row, valid_i64)));
+    if (valid) limit = max(0ll, min(width, load_index(valid, row, valid_i64)));
     const uint8_t* m = mask + row * width;
     long long* o = out_idx + row * width;
     long long offset = 0;

@@ -1,7 +1,10 @@
 """Filler conversion of the ragged ops on the host: ``element_bits`` (the bytes every GPU fill writes) and the CPU pad fill
 against ``static_cast<scalar_t>(double)`` as torch spells it, ``torch.tensor(v, dtype=float64).to(dtype)``: round to
 nearest even, out of range -> ±inf, NaN stays NaN, -0.0 stays -0.0.  Also pins that the cached conversion does not
-depend on call order (-0.0 and 0.0 compare and hash equal)."""
+depend on call order (-0.0 and 0.0 compare and hash equal).
+
+The shared f16 / bf16 conversions of csrc/accv_numeric.h (software flavour) have no entry point of their own; they are
+pinned through ``accv_matched_focal_loss_bwd_host``, whose gradient can be made to equal a chosen float32 exactly."""
 import math
 import struct
 
@@ -129,3 +132,69 @@ def test_cpu_pad_fill_integer_and_bool(dtype):
 
     b = RaggedBatch(torch.zeros(2, 3, dtype=torch.bool), sample_sizes=torch.tensor([0, 2]))
     assert b.with_padded_set_to(0.5).tensor.tolist() == [[True, True, True], [False, False, True]]
+
+
+# ---- the shared f16 / bf16 conversions (csrc/accv_numeric.h), through the host twin of the matched focal loss --------------
+# One frame per value, Q = C = 1, no pair (all background), logit +inf, gamma = 0, no alpha blend, avg_factor = 1: the
+# element's derivative is sigmoid(+inf) = 1 exactly, so the gradient written is narrow((w * 1) * grad_out[b]) with grad_out
+# float32 and w the query weight widened from the logits dtype (1 without weights).
+HALVES = [torch.float16, torch.bfloat16]
+
+
+def _host_gradient(dtype, grad_out, weights=None):
+    from accvlab.batching_helpers import RaggedBatch, matched_focal_loss
+
+    B = grad_out.numel()
+    empty = lambda dt: RaggedBatch(torch.zeros((B, 1), dtype=dt), sample_sizes=torch.zeros((B,), dtype=torch.int64))
+    logits = torch.full((B, 1, 1), math.inf, dtype=dtype, requires_grad=True)
+    out = matched_focal_loss(logits, empty(torch.int64), empty(torch.int64), empty(torch.int64), alpha=-1.0, gamma=0.0,
+                             query_weights=weights, avg_factor=1.0)
+    out.backward(grad_out)
+    return logits.grad.reshape(B)
+
+
+def _narrowing_inputs(dtype):
+    vals = [v for v in COMMON + PER_TYPE[dtype] if not math.isnan(v) and abs(v) < 3.5e38 or math.isinf(v)]
+    x = torch.tensor(vals, dtype=torch.float64).to(torch.float32)
+    # every float32 around the boundaries: subnormal / normal, largest finite / infinity, and ties between neighbours
+    g = torch.Generator().manual_seed(5)
+    bits = torch.randint(-2 ** 31, 2 ** 31 - 1, (200000,), generator=g, dtype=torch.int64).to(torch.int32)
+    rnd = bits.view(torch.float32)
+    tiny = torch.tensor(6.5e-5 if dtype == torch.float16 else 2.4e-38) * torch.rand(50000, generator=g)   # subnormal results
+    ulp = torch.arange(-40, 41, dtype=torch.int32)
+    edge = torch.tensor([65504.0, 65520.0, 2.0 ** -14, 2.0 ** -24, 2.0 ** -25, 1.0 + 2.0 ** -11, 3.3895313892515355e38,
+                         3.3961775292304e38, 2.0 ** -126, 1.0 + 2.0 ** -8], dtype=torch.float32)
+    near = (edge.view(torch.int32)[:, None] + ulp[None, :]).reshape(-1).view(torch.float32)
+    x = torch.cat([x, rnd, tiny, -tiny, near, -near])
+    return x[~torch.isnan(x)]
+
+
+@pytest.mark.parametrize("dtype", HALVES, ids=["float16", "bfloat16"])
+def test_shared_narrowing_is_the_torch_cast(dtype):
+    x = _narrowing_inputs(dtype)
+    got = _host_gradient(dtype, x)
+    want = x.to(dtype)
+    assert not torch.isnan(want).any()
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+    for v in (0.0, -0.0, 65504.0, 65519.0, 65520.0, 2.0 ** -24, 2.0 ** -25, 1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11):   # named cases
+        one = _host_gradient(dtype, torch.tensor([v], dtype=torch.float32))
+        assert one.view(torch.int16).item() == torch.tensor([v], dtype=torch.float32).to(dtype).view(torch.int16).item(), v
+
+
+@pytest.mark.parametrize("dtype", HALVES, ids=["float16", "bfloat16"])
+def test_shared_narrowing_keeps_nan(dtype):
+    nans = torch.tensor([0x7fc00000, -0x400000, 0x7f800001, 0x7fffffff, -1, 0x7f80ffff, 0x7f810000],
+                        dtype=torch.int64).to(torch.int32).view(torch.float32)
+    assert torch.isnan(nans).all()
+    assert torch.isnan(_host_gradient(dtype, nans).float()).all()
+
+
+@pytest.mark.parametrize("dtype", HALVES, ids=["float16", "bfloat16"])
+def test_shared_widening_is_exact(dtype):
+    """Every 16-bit pattern as a query weight: widen, times 1, narrow gives the pattern back (NaN: some NaN)."""
+    w = torch.arange(-2 ** 15, 2 ** 15, dtype=torch.int32).to(torch.int16).view(dtype)
+    got = _host_gradient(dtype, torch.ones(w.numel(), dtype=torch.float32), weights=w.reshape(-1, 1))
+    nan = torch.isnan(w.float())
+    assert torch.equal(got.view(torch.int16)[~nan], w.view(torch.int16)[~nan])
+    assert torch.isnan(got.float()[nan]).all()
+    assert torch.equal(got.float()[~nan], w.float()[~nan])   # and torch widens to the same float32
