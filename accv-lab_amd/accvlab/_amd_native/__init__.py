@@ -52,6 +52,12 @@ CR_L1 = 0
 CR_SMOOTH_L1 = 2
 MF_IDX_I64 = 1
 MF_LABELS_I64 = 2
+MB_IDX_I64 = 1
+MB_CXCYWH = 2
+MB_IOU_NONE = 0
+MB_IOU = 1
+MB_GIOU = 2
+MB_MAX_D = 16
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -125,6 +131,15 @@ SIGNATURES = {
                                           _vp]),
     "accv_matched_focal_loss_bwd_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll,
                                               _ll, _vp, _vp]),
+    # matched box loss (params: a MatchedBoxParams by address; out is [2, B])
+    "accv_matched_box_loss_workspace_bytes": (_sz, [_ll, _ll, _ll]),
+    "accv_matched_box_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _sz,
+                                   _vp]),
+    "accv_matched_box_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp,
+                                       _vp]),
+    "accv_matched_box_loss_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
+    "accv_matched_box_loss_bwd_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp,
+                                            _vp]),
     # centre-point regression (maps: host arrays of pointers and channel counts; params: a CenterRegressionParams by address)
     "accv_gather_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
     "accv_scatter_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
@@ -173,6 +188,13 @@ class MatchedFocalParams(ctypes.Structure):
                 ("avg_mode", ctypes.c_int), ("avg_factor_dev", ctypes.c_void_p)]
 
 
+class MatchedBoxParams(ctypes.Structure):
+    """accv_matched_box_params of include/accv_hip.h"""
+    _fields_ = [("iou_eps", ctypes.c_double), ("avg_factor", ctypes.c_double), ("code_weights", ctypes.c_double * 16),
+                ("avg_mode", ctypes.c_int), ("iou_kind", ctypes.c_int), ("avg_factor_dev", ctypes.c_void_p),
+                ("code_weights_dev", ctypes.c_void_p), ("query_weights", ctypes.c_void_p)]
+
+
 class CenterRegressionParams(ctypes.Structure):
     """accv_center_regression_params of include/accv_hip.h"""
     _fields_ = [("kind", ctypes.c_int), ("avg_mode", ctypes.c_int), ("beta", ctypes.c_float), ("avg_factor", ctypes.c_float)]
@@ -193,7 +215,8 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 # interpreter lock for the duration of the call — the trampoline keeps it
 _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
              "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
-             "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host"}
+             "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
+             "accv_matched_box_loss_bwd_host"}
 
 
 def _fast_entry(fn, res, args):

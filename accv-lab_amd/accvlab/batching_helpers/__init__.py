@@ -34,6 +34,7 @@ from .batched_processing_py import (
 
 from .fused import matched_pair_loss_sum  # (extension) gathers + per-object loss + masked sum in one launch
 from .matched_focal import matched_focal_loss  # (extension) sigmoid focal loss over all queries against the matched labels
+from .matched_box import matched_box_loss  # (extension) L1 + GIoU / IoU box loss over the matched pairs
 from .assignment import batched_linear_sum_assignment  # (extension) per-frame Hungarian matching in one launch
 from .matching_cost import batched_matching_cost, batched_hungarian_match  # (extension) fused matching-cost matrices
 
@@ -58,6 +59,7 @@ __all__ = [
     "get_compact_lists",
     "get_indices_from_mask",
     "get_mask_from_indices",
+    "matched_box_loss",
     "matched_focal_loss",
     "matched_pair_loss_sum",
     "squeeze_except_batch_and_sample",

@@ -1,0 +1,261 @@
+"""(extension) Box regression loss of a set-prediction head (DETR / Deformable-DETR / StreamPETR) over the matched pairs:
+the L1 term and the GIoU (or IoU) term in one operator — the link of the loss chain between
+``batched_linear_sum_assignment`` and the criterion's weighted sum, next to ``matched_focal_loss``.
+
+The torch composition gathers both sides through the match indices, converts the box format and runs about 25
+element-wise launches forward and twice that backward on a few thousand numbers.  Here: two launches forward, one
+write-only launch backward.
+
+GPU tensors run the HIP kernels (``accv_matched_box_loss`` / ``_bwd``); CPU tensors run the host implementation of the
+same operation sequence (``accv_matched_box_loss_host`` / ``_bwd_host``).  There is no CPU fallback for GPU tensors.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence, Tuple, Union
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from .. import _amd_native as _nat
+from .ragged import RaggedBatch
+
+__all__ = ["matched_box_loss"]
+
+_WHO = "matched_box_loss"
+_DTYPES = _nat.FLOAT_DTYPE_CODES
+_IOU_KINDS = {None: _nat.MB_IOU_NONE, "iou": _nat.MB_IOU, "giou": _nat.MB_GIOU}
+_FORMATS = {"xyxy": 0, "cxcywh": _nat.MB_CXCYWH}
+
+
+class _Call:
+    """what the forward and the backward C-ABI calls of one invocation share"""
+
+    def __init__(self, boxes, gt, pind, gind, counts, flags, params, keep):
+        self.gt, self.pind, self.gind, self.counts = gt, pind, gind, counts
+        self.params, self.keep = params, keep   # keep: the tensors the parameter struct points into
+        self.dev = boxes.device
+        self.B, self.Q, self.D = (int(v) for v in boxes.shape)
+        self.G, self.K = int(gt.shape[1]), int(pind.shape[1])
+        self.flags = flags
+        self.out_dtype = torch.float64 if boxes.dtype == torch.float64 else torch.float32
+
+    def inputs(self, boxes):
+        return (boxes.data_ptr(), self.gt.data_ptr(), self.pind.data_ptr(), self.gind.data_ptr(), self.counts.data_ptr())
+
+    def shape(self, boxes):
+        # a dimension of extent 1 may carry any stride
+        sb = boxes.stride(0) if self.B > 1 else self.Q * max(boxes.stride(1), self.D)
+        sq = boxes.stride(1) if self.Q > 1 else self.D
+        return (_DTYPES[boxes.dtype], self.flags, self.B, self.Q, self.D, self.G, self.K, sb, sq,
+                ctypes.addressof(self.params))
+
+
+class _MatchedBoxLoss(torch.autograd.Function):
+    """-> (L1 sums [B], IoU sums [B]), the two rows of one [2, B] tensor"""
+
+    @staticmethod
+    def forward(ctx, call, boxes):
+        dev = call.dev
+        run = call.B * call.Q * call.K > 0
+        out = (torch.empty if run else torch.zeros)((2, call.B), dtype=call.out_dtype, device=dev)
+        denom = torch.empty((), dtype=torch.float64, device=dev)
+        if run:
+            lib = _nat.lib()
+            if dev.type == "cuda":
+                nbytes = lib.accv_matched_box_loss_workspace_bytes(call.B, call.Q, call.D)
+                ws = _nat.workspace(nbytes, dev)
+                with _nat.device_guard(dev):
+                    _nat.check(lib.accv_matched_box_loss(*call.inputs(boxes), *call.shape(boxes), out.data_ptr(),
+                                                         denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
+            else:
+                _nat.check(lib.accv_matched_box_loss_host(*call.inputs(boxes), *call.shape(boxes), out.data_ptr(),
+                                                          denom.data_ptr()), _WHO)
+        ctx.call, ctx.run = call, run
+        ctx.save_for_backward(boxes, denom)
+        ctx.set_materialize_grads(False)   # an unused output arrives as None and goes down as a null pointer
+        return out[0], out[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_l1, grad_iou):
+        call = ctx.call
+        boxes, denom = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        if not ctx.run:   # no pair anywhere: nothing depends on the boxes
+            return None, torch.zeros(boxes.shape, dtype=boxes.dtype, device=call.dev)
+        grad = torch.empty(boxes.shape, dtype=boxes.dtype, device=call.dev)   # contiguous, written completely
+        grad_l1 = None if grad_l1 is None else grad_l1.to(call.out_dtype).contiguous()
+        grad_iou = None if grad_iou is None else grad_iou.to(call.out_dtype).contiguous()
+        lib = _nat.lib()
+        args = (*call.inputs(boxes), None if grad_l1 is None else grad_l1.data_ptr(),
+                None if grad_iou is None else grad_iou.data_ptr(), denom.data_ptr(), *call.shape(boxes), grad.data_ptr())
+        if call.dev.type == "cuda":
+            with _nat.device_guard(call.dev):
+                _nat.check(lib.accv_matched_box_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
+        else:
+            _nat.check(lib.accv_matched_box_loss_bwd_host(*args), _WHO + " backward")
+        return None, grad
+
+
+def _ragged(name, rb, what, dims):
+    if not isinstance(rb, RaggedBatch):
+        raise TypeError(f"{_WHO}: {name} must be a RaggedBatch {what}, got {type(rb).__name__}")
+    t = rb.tensor
+    if rb.num_batch_dims != 1 or t.dim() != dims or rb.non_uniform_dim != 1:
+        raise ValueError(f"{_WHO}: {name} must be a RaggedBatch {what} with non_uniform_dim 1, got shape {tuple(t.shape)}, "
+                         f"non_uniform_dim {rb.non_uniform_dim}")
+    return t.detach().contiguous()
+
+
+def _index(name, rb):
+    t = _ragged(name, rb, "[B, K]", 2)
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{_WHO}: {name} must be int32 or int64, got {t.dtype}")
+    return t
+
+
+def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: RaggedBatch, gt_ind: RaggedBatch, *,
+                     box_format: str = "xyxy", iou_kind: Optional[str] = "giou",
+                     code_weights: Optional[Union[Sequence[float], torch.Tensor]] = None,
+                     query_weights: Optional[torch.Tensor] = None, iou_eps: float = 1e-6,
+                     avg_factor: Optional[Union[float, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-frame box regression losses ``(loss_l1 [B], loss_iou [B])`` over the matched pairs, both divided by the number
+    of matched pairs and neither multiplied by a term weight: a criterion forms
+    ``w_l1 * loss_l1 + w_giou * loss_iou + w_cls * matched_focal_loss(...)``.
+
+    Args:
+        pred_boxes: dense ``[B, Q, D]``, float32 / float16 / bfloat16 / float64, ``1 <= D <= 16``.  Unit stride in the
+            last dimension; the batch and query strides are free (``code[..., :4]`` of a wider regression output needs
+            no copy).
+        gt_boxes: RaggedBatch ``[B, G*, D]`` of the same dtype.  Never differentiated.
+        pred_ind, gt_ind: RaggedBatch ``[B, K]``, int32 / int64, one dtype — what ``batched_linear_sum_assignment`` /
+            ``batched_hungarian_match`` return.  ONLY ``pred_ind.sample_sizes`` is read (on the device, clamped to
+            ``[0, K]``); comparing the two would cost a synchronisation.
+        box_format: ``"xyxy"`` or ``"cxcywh"`` (both sides; converted as mmdet's ``bbox_cxcywh_to_xyxy``, the L1 term is
+            taken on the raw coordinates as DETR does).
+        iou_kind: ``"giou"``, ``"iou"`` or ``None`` (L1 only: ``loss_iou`` is zeros and nothing is evaluated for it).  An
+            IoU kind requires ``D == 4``.
+        code_weights: optional ``[D]`` (mmdet3d's ``code_weights``), multiplies the L1 term per coordinate: a Python
+            sequence (used in the arithmetic type, float32 or float64) or a tensor of the boxes' dtype on their device.
+        query_weights: optional dense ``[B, Q]`` of the boxes' dtype; multiplies both terms of that query's pair.
+        iou_eps: floor of the union and of the enclosing area (mmdet's ``eps``).
+        avg_factor: ``None`` divides by ``max(M, 1)`` with ``M = sum_b clamp(n_b, 0, K)`` counted on the device — the
+            number ``matched_focal_loss`` divides by; a Python number is used as given (``1.0`` gives raw sums); a 0-d
+            float32 tensor on the boxes' device (an all-reduced count) is read on the device.
+        No gradient flows to either weight or to ``avg_factor``.
+
+    Definition (its float64 evaluation with autograd on the dtype-rounded inputs is what the tests pin)::
+
+        for b, j < clamp(n_b, 0, K):                       # ascending j
+            q, g = pred_ind[b, j], gt_ind[b, j]
+            if 0 <= q < Q and 0 <= g < G_max and no lower j named q:      # a pair with both indices in range names q
+                p, t = pred_boxes[b, q], gt_boxes[b, g]
+                loss_l1[b]  += w[b, q] * sum_d cw[d] * |p[d] - t[d]|
+                loss_iou[b] += w[b, q] * (1 - bbox_overlaps(xyxy(p), xyxy(t), mode=iou_kind, is_aligned=True, eps=iou_eps))
+        loss_l1, loss_iou = loss_l1 / factor, loss_iou / factor
+
+    The pair rule is ``matched_focal_loss``'s, so both losses always agree on which queries are matched: indices outside
+    their range are skipped, not wrapped; a query named twice takes the pair in the lowest slot; slots at or past ``n_b``
+    are never read.  A frame without pairs gives 0.  ``B``, ``Q`` or ``K`` of 0 give zeros and launch nothing.
+
+    Returns two ``[B]`` tensors, float32 (float64 for float64 boxes).  Differentiable w.r.t. ``pred_boxes`` only, for
+    either or both outputs (no double backward); the gradient has the boxes' dtype, is contiguous and written completely,
+    ``+0`` for unmatched queries.  It is the closed-form chain rule with float64 autograd's conventions where the
+    definition is not smooth: an exact tie of a maximum / minimum splits the gradient evenly, a floor that fires passes
+    none, ``|0|`` has gradient 0.  float16 / bfloat16 boxes are widened exactly and evaluated in float32, float64 in
+    float64; sums are accumulated in float64 in a fixed order, so forward and backward are bitwise reproducible.  Two
+    launches forward, one backward (no zero fill, no atomics), on torch's current stream, without host synchronisation or
+    read-back: both directions can be captured into a graph.
+
+    Special values: a NaN in a matched prediction makes its frame's sums and that query's gradient NaN (with an IoU kind
+    all four components, otherwise the component of the NaN coordinate); rows of unmatched queries are never read.
+    """
+    if not isinstance(pred_boxes, torch.Tensor):
+        raise TypeError(f"{_WHO}: pred_boxes must be a tensor, got {type(pred_boxes).__name__}")
+    if pred_boxes.dim() != 3:
+        raise ValueError(f"{_WHO}: pred_boxes must be [B, Q, D], got shape {tuple(pred_boxes.shape)}")
+    if pred_boxes.dtype not in _DTYPES:
+        raise TypeError(f"{_WHO}: pred_boxes must be float32, float16, bfloat16 or float64, got {pred_boxes.dtype}")
+    if pred_boxes.shape[-1] > 1 and pred_boxes.stride(-1) != 1:
+        raise ValueError(f"{_WHO}: the last dimension of pred_boxes must have unit stride, got stride "
+                         f"{pred_boxes.stride(-1)}")
+    dev = pred_boxes.device
+    if dev.type not in ("cuda", "cpu"):
+        raise RuntimeError(f"{_WHO}: unsupported device {dev}")
+    B, Q, D = (int(v) for v in pred_boxes.shape)
+    if not 1 <= D <= _nat.MB_MAX_D:
+        raise ValueError(f"{_WHO}: needs 1 <= D <= {_nat.MB_MAX_D}, got D = {D}")
+    if Q > 1 and pred_boxes.stride(1) < D or B > 1 and pred_boxes.stride(0) < 0:
+        raise ValueError(f"{_WHO}: overlapping or reversed pred_boxes (strides {pred_boxes.stride()}) are not supported")
+    if box_format not in _FORMATS:
+        raise ValueError(f"{_WHO}: box_format must be 'xyxy' or 'cxcywh', got {box_format!r}")
+    if iou_kind not in _IOU_KINDS:
+        raise ValueError(f"{_WHO}: iou_kind must be 'giou', 'iou' or None, got {iou_kind!r}")
+    if iou_kind is not None and D != 4:
+        raise ValueError(f"{_WHO}: iou_kind {iou_kind!r} needs D == 4, got D = {D}")
+    iou_eps = float(iou_eps)
+    if not iou_eps >= 0.0:
+        raise ValueError(f"{_WHO}: iou_eps must be >= 0, got {iou_eps}")
+
+    gt = _ragged("gt_boxes", gt_boxes, "[B, G*, D]", 3)
+    if gt.dtype != pred_boxes.dtype:
+        raise TypeError(f"{_WHO}: gt_boxes is {gt.dtype}, pred_boxes {pred_boxes.dtype}")
+    if int(gt.shape[2]) != D:
+        raise ValueError(f"{_WHO}: gt_boxes has {gt.shape[2]} coordinates, pred_boxes {D}")
+    pind = _index("pred_ind", pred_ind)
+    gind = _index("gt_ind", gt_ind)
+    if pind.dtype != gind.dtype:
+        raise TypeError(f"{_WHO}: pred_ind is {pind.dtype}, gt_ind {gind.dtype}: one index dtype expected")
+    if pind.shape != gind.shape:
+        raise ValueError(f"{_WHO}: pred_ind has shape {tuple(pind.shape)}, gt_ind {tuple(gind.shape)}")
+    sizes = pred_ind.sample_sizes
+    if sizes.dim() != 1 or sizes.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{_WHO}: pred_ind.sample_sizes must be int32 or int64 [B]")
+    weights = query_weights
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (B, Q):
+            raise ValueError(f"{_WHO}: query_weights must be a tensor [B, Q] = [{B}, {Q}], got "
+                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+        if weights.dtype != pred_boxes.dtype:
+            raise TypeError(f"{_WHO}: query_weights is {weights.dtype}, pred_boxes {pred_boxes.dtype}")
+        weights = weights.detach().contiguous()
+    cw_dev, cw_values = None, None
+    if isinstance(code_weights, torch.Tensor):
+        if tuple(code_weights.shape) != (D,):
+            raise ValueError(f"{_WHO}: code_weights must have shape [{D}], got {tuple(code_weights.shape)}")
+        if code_weights.dtype != pred_boxes.dtype:
+            raise TypeError(f"{_WHO}: code_weights is {code_weights.dtype}, pred_boxes {pred_boxes.dtype}")
+        if code_weights.device != dev:
+            raise ValueError(f"{_WHO}: code_weights is on {code_weights.device}, pred_boxes on {dev}")
+        cw_dev = code_weights.detach().contiguous()
+    elif code_weights is not None:
+        try:
+            cw_values = [float(v) for v in code_weights]
+        except TypeError:
+            raise TypeError(f"{_WHO}: code_weights must be a sequence of numbers or a tensor, got "
+                            f"{type(code_weights).__name__}") from None
+        if len(cw_values) != D:
+            raise ValueError(f"{_WHO}: code_weights must have shape [{D}], got {len(cw_values)} values")
+    for name, t in (("gt_boxes", gt), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", sizes),
+                    ("query_weights", weights)):
+        if t is None:
+            continue
+        if t.device != dev:
+            raise ValueError(f"{_WHO}: {name} is on {t.device}, pred_boxes on {dev}")
+        if int(t.shape[0]) != B:
+            raise ValueError(f"{_WHO}: {name} has batch size {t.shape[0]}, pred_boxes {B}")
+
+    mode, value, avg_dev = _nat.avg_factor_args(avg_factor, dev, _WHO, ValueError, "the boxes' device")
+    counts = sizes.detach().to(torch.int64).contiguous()
+    params = _nat.MatchedBoxParams()
+    params.iou_eps, params.avg_factor, params.avg_mode, params.iou_kind = iou_eps, value, mode, _IOU_KINDS[iou_kind]
+    for d in range(D):
+        params.code_weights[d] = 1.0 if cw_values is None else cw_values[d]
+    params.avg_factor_dev = None if avg_dev is None else avg_dev.data_ptr()
+    params.code_weights_dev = None if cw_dev is None else cw_dev.data_ptr()
+    params.query_weights = None if weights is None else weights.data_ptr()
+    flags = (_nat.MB_IDX_I64 if pind.dtype == torch.int64 else 0) | _FORMATS[box_format]
+    call = _Call(pred_boxes, gt, pind, gind, counts, flags, params, (avg_dev, cw_dev, weights))
+    return _MatchedBoxLoss.apply(call, pred_boxes)

@@ -229,3 +229,89 @@ def focal_class_loss_fused(pred_logits, gt_labels: bh.RaggedBatch, pred_ind: bh.
                            alpha=0.25, gamma=2.0):
     """The same loss through ``bh.matched_focal_loss``: two launches forward, one backward, no one-hot target."""
     return bh.matched_focal_loss(pred_logits, gt_labels, pred_ind, gt_ind, alpha=alpha, gamma=gamma)
+
+
+# ------------------------------------------------------------------------------------------------ box regression loss
+def _to_xyxy(b: torch.Tensor, box_format: str) -> torch.Tensor:
+    """mmdet's ``bbox_cxcywh_to_xyxy`` (or the identity)"""
+    if box_format != "cxcywh":
+        return b
+    cx, cy, w, h = b.unbind(-1)
+    return torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
+
+
+def _aligned_overlaps(a: torch.Tensor, b: torch.Tensor, mode: str, eps: float = EPS) -> torch.Tensor:
+    """mmdet's ``bbox_overlaps(a, b, mode, is_aligned=True, eps)`` of xyxy boxes ``[..., 4]``"""
+    area_a = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1])
+    area_b = (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
+    wh = (torch.min(a[..., 2:], b[..., 2:]) - torch.max(a[..., :2], b[..., :2])).clamp(min=0)
+    overlap = wh[..., 0] * wh[..., 1]
+    union = torch.max(area_a + area_b - overlap, overlap.new_tensor(eps))
+    ious = overlap / union
+    if mode == "iou":
+        return ious
+    enclose_wh = (torch.max(a[..., 2:], b[..., 2:]) - torch.min(a[..., :2], b[..., :2])).clamp(min=0)
+    enclose = torch.max(enclose_wh[..., 0] * enclose_wh[..., 1], overlap.new_tensor(eps))
+    return ious - (enclose - union) / enclose
+
+
+def box_loss_composed(pred_boxes, gt_boxes: bh.RaggedBatch, pred_ind: bh.RaggedBatch, gt_ind: bh.RaggedBatch,
+                      box_format="cxcywh", iou_kind="giou", code_weights=None):
+    """The box regression loss a DETR-style head trains with, per frame ``(loss_l1 [B], loss_iou [B])``, as the composition
+    a user writes from the ragged operators and torch: both sides gathered through the match indices, the format
+    conversion, L1 on the raw coordinates, ``1 - GIoU`` as mmdet's aligned ``bbox_overlaps``, masked per-frame sums and
+    the division by the number of matched pairs."""
+    box_g = bh.batched_indexing_access(gt_boxes, gt_ind)
+    box_p = bh.batched_indexing_access(pred_boxes, pred_ind)
+    diff = (box_p.tensor - box_g.tensor).abs()
+    if code_weights is not None:
+        diff = diff * torch.as_tensor(code_weights, dtype=diff.dtype, device=diff.device)
+    num_pos = pred_ind.sample_sizes.sum().clamp(min=1)
+    loss_l1 = bh.sum_over_targets(box_g.create_with_sample_sizes_like_self(diff.sum(-1), non_uniform_dim=1)) / num_pos
+    if iou_kind is None:
+        return loss_l1, torch.zeros_like(loss_l1)
+    term = 1.0 - _aligned_overlaps(_to_xyxy(box_p.tensor, box_format), _to_xyxy(box_g.tensor, box_format), iou_kind)
+    loss_iou = bh.sum_over_targets(box_g.create_with_sample_sizes_like_self(term, non_uniform_dim=1)) / num_pos
+    return loss_l1, loss_iou
+
+
+def box_loss_fused(pred_boxes, gt_boxes: bh.RaggedBatch, pred_ind: bh.RaggedBatch, gt_ind: bh.RaggedBatch,
+                   box_format="cxcywh", iou_kind="giou", code_weights=None):
+    """The same two losses through ``bh.matched_box_loss``: two launches forward, one write-only launch backward."""
+    return bh.matched_box_loss(pred_boxes, gt_boxes, pred_ind, gt_ind, box_format=box_format, iou_kind=iou_kind,
+                               code_weights=code_weights, iou_eps=EPS)
+
+
+# DETR's weights with the focal class term of Deformable-DETR: class 2, L1 5, GIoU 2 — in the matcher and in the loss
+CRITERION_WEIGHTS = dict(cls=2.0, l1=5.0, giou=2.0)
+
+
+def set_criterion_match(pred_logits, pred_boxes, gt_labels: bh.RaggedBatch, gt_boxes: bh.RaggedBatch, box_format="cxcywh"):
+    """-> (pred_ind, gt_ind): cost matrices and assignment on the device, two launches, no host synchronisation"""
+    w = CRITERION_WEIGHTS
+    return bh.batched_hungarian_match(pred_logits.detach(), gt_labels, pred_boxes.detach(), gt_boxes, class_cost="focal",
+                                      class_weight=w["cls"], l1_weight=w["l1"], giou_weight=w["giou"],
+                                      box_format=box_format, iou_eps=EPS, check=False)[:2]
+
+
+def set_criterion_fused(pred_logits, pred_boxes, gt_labels: bh.RaggedBatch, gt_boxes: bh.RaggedBatch, box_format="cxcywh",
+                        matching=None):
+    """The whole set-prediction criterion on the device, per frame ``[B]``: matching cost -> assignment ->
+    ``matched_focal_loss`` + ``matched_box_loss`` with DETR's weights.  Both losses see the same pairs and divide by the
+    same number of pairs; nothing synchronises with the host."""
+    w = CRITERION_WEIGHTS
+    pred_ind, gt_ind = matching or set_criterion_match(pred_logits, pred_boxes, gt_labels, gt_boxes, box_format)
+    loss_cls = bh.matched_focal_loss(pred_logits, gt_labels, pred_ind, gt_ind)
+    loss_l1, loss_giou = bh.matched_box_loss(pred_boxes, gt_boxes, pred_ind, gt_ind, box_format=box_format, iou_kind="giou",
+                                             iou_eps=EPS)
+    return w["cls"] * loss_cls + w["l1"] * loss_l1 + w["giou"] * loss_giou
+
+
+def set_criterion_composed(pred_logits, pred_boxes, gt_labels: bh.RaggedBatch, gt_boxes: bh.RaggedBatch, box_format="cxcywh",
+                           matching=None):
+    """The same criterion from ``focal_class_loss_composed`` and ``box_loss_composed``."""
+    w = CRITERION_WEIGHTS
+    pred_ind, gt_ind = matching or set_criterion_match(pred_logits, pred_boxes, gt_labels, gt_boxes, box_format)
+    loss_cls = focal_class_loss_composed(pred_logits, gt_labels, pred_ind, gt_ind)
+    loss_l1, loss_giou = box_loss_composed(pred_boxes, gt_boxes, pred_ind, gt_ind, box_format=box_format, iou_kind="giou")
+    return w["cls"] * loss_cls + w["l1"] * loss_l1 + w["giou"] * loss_giou

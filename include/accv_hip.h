@@ -531,6 +531,68 @@ int accv_matched_focal_loss_bwd_host(const void* logits, const void* gt_labels, 
                                      long long G, long long K, long long stride_b, long long stride_q,
                                      const accv_matched_focal_params* params, void* grad_logits);
 
+/* -------------------------------------------------------------------------------------------------- matched box loss
+ * The box regression loss of a set-prediction head over the matched pairs, both terms in one pass:
+ *     out[0][b] = sum over the pairs (q, g) of frame b of  w[b, q] * sum_d cw[d] |p[b, q, d] - gt[b, g, d]| / denom
+ *     out[1][b] = sum over the pairs of  w[b, q] * (1 - giou(p, gt))  (ACCV_MB_GIOU),  (1 - iou) (ACCV_MB_IOU),  0 (ACCV_MB_IOU_NONE)
+ * IoU / GIoU as in accv_matching_cost (mmdet bbox_overlaps, union and enclosure floored at iou_eps, maxima and minima
+ * keep NaN), boxes xyxy or, with ACCV_MB_CXCYWH, cxcywh; an IoU kind needs D == 4, the L1 term takes 1 <= D <= 16.
+ * Pairs: the rule of accv_matched_focal_loss.  The slots j < n_b = clamp(counts[b], 0, K) (counts: int64 [B]) of pred_ind /
+ * gt_ind [B, K] (int32, int64 with ACCV_MB_IDX_I64) name query pred_ind[b, j] when 0 <= pred_ind < Q and 0 <= gt_ind < G;
+ * the LOWEST slot that names a query is its pair, other slots are skipped, slots at or past n_b are never read.
+ * pred_boxes [B, Q, D] of dtype 0 f32, 1 f16, 2 bf16, 3 f64: element (b, q, d) at b * stride_b + q * stride_q + d, strides
+ * in elements, stride_q >= D.  gt_boxes: contiguous [B, G, D] of the same dtype.  f16 / bf16 are widened exactly and
+ * evaluated in f32, f64 in f64; sums are accumulated in f64.  denom as for accv_matched_focal_loss.
+ * out: [2, B] f32 (f64 for dtype 3), row 0 the L1 sums, row 1 the IoU sums; out_denom one f64 scalar that the backward
+ * reads.  workspace: accv_matched_box_loss_workspace_bytes(B, Q, D) bytes of device memory, 16-byte aligned.  Two
+ * launches, no atomics on global memory, no host synchronisation, bitwise reproducible.  Returns ACCV_EINVAL (null params,
+ * negative size, unknown dtype / flag / IoU kind / avg mode, D outside [1, 16], an IoU kind with D != 4, K above 2^31 - 1,
+ * stride_q < D, null or misaligned pointers) or ACCV_EWORKSPACE before touching the device, ACCV_ELAUNCH if a launch
+ * fails.  B * Q == 0 launches nothing and writes nothing. */
+#define ACCV_MB_IDX_I64 1u
+#define ACCV_MB_CXCYWH 2u
+#define ACCV_MB_IOU_NONE 0
+#define ACCV_MB_IOU 1
+#define ACCV_MB_GIOU 2
+/* the scalar parameters and optional operands, host memory, read during the call */
+typedef struct accv_matched_box_params {
+    double iou_eps;
+    double avg_factor;            /* the denominator of ACCV_FL_AVG_VALUE */
+    double code_weights[16];      /* cw[d] for d < D, rounded to the arithmetic type; read when code_weights_dev is NULL */
+    int avg_mode;                 /* ACCV_FL_AVG_NUM_POS, ACCV_FL_AVG_VALUE or ACCV_FL_AVG_DEVICE; the backward ignores it */
+    int iou_kind;                 /* ACCV_MB_IOU_NONE, ACCV_MB_IOU or ACCV_MB_GIOU */
+    const float* avg_factor_dev;  /* the f32 scalar of ACCV_FL_AVG_DEVICE */
+    const void* code_weights_dev; /* NULL or [D] of the boxes' dtype in the boxes' memory */
+    const void* query_weights;    /* NULL or contiguous [B, Q] of the boxes' dtype */
+} accv_matched_box_params;
+size_t accv_matched_box_loss_workspace_bytes(long long B, long long Q, long long D);
+int accv_matched_box_loss(const void* pred_boxes, const void* gt_boxes, const void* pred_ind, const void* gt_ind,
+                          const long long* counts, int dtype, unsigned flags, long long B, long long Q, long long D, long long G,
+                          long long K, long long stride_b, long long stride_q, const accv_matched_box_params* params, void* out,
+                          double* out_denom, void* workspace, size_t workspace_bytes, void* stream);
+/* Its backward: grad_boxes (contiguous [B, Q, D], the boxes' dtype, round to nearest even) is written completely, every
+ * element exactly once: (s1 * dL1 + s2 * dIoU) * w[b, q] with s1 = grad_l1[b] / *denom and s2 = grad_iou[b] / *denom
+ * formed in f64 and rounded to the arithmetic type; +0 for a query without a pair.  grad_l1 and grad_iou ([B] each, the
+ * dtype of out) are the gradients of the two rows of out; either may be NULL and then counts as zeros.  denom is
+ * out_denom of the forward.  The derivative follows float64 autograd over the definition: an exact tie of a
+ * maximum / minimum splits evenly, a floor that fires passes nothing, |0| has derivative 0.  One launch; needs no
+ * initialised gradient, uses no atomics. */
+int accv_matched_box_loss_bwd(const void* pred_boxes, const void* gt_boxes, const void* pred_ind, const void* gt_ind,
+                              const long long* counts, const void* grad_l1, const void* grad_iou, const double* denom, int dtype,
+                              unsigned flags, long long B, long long Q, long long D, long long G, long long K, long long stride_b,
+                              long long stride_q, const accv_matched_box_params* params, void* grad_boxes, void* stream);
+/* The same on the host (same operation sequence per pair; a frame's sums are accumulated in query order); every pointer
+ * is host memory.  Block the calling thread. */
+int accv_matched_box_loss_host(const void* pred_boxes, const void* gt_boxes, const void* pred_ind, const void* gt_ind,
+                               const long long* counts, int dtype, unsigned flags, long long B, long long Q, long long D,
+                               long long G, long long K, long long stride_b, long long stride_q,
+                               const accv_matched_box_params* params, void* out, double* out_denom);
+int accv_matched_box_loss_bwd_host(const void* pred_boxes, const void* gt_boxes, const void* pred_ind, const void* gt_ind,
+                                   const long long* counts, const void* grad_l1, const void* grad_iou, const double* denom,
+                                   int dtype, unsigned flags, long long B, long long Q, long long D, long long G, long long K,
+                                   long long stride_b, long long stride_q, const accv_matched_box_params* params,
+                                   void* grad_boxes);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */
