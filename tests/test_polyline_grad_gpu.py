@@ -212,8 +212,14 @@ def test_f32_matches_float64_reference(b, npnt, nq, dims, relative):
 def test_f32_long_polyline_takes_the_workspace_path():
     from accvlab import _amd_native as nat
 
+    import polyline_edges_cases as pc   # the launch plan restated (imports this module: not at the top)
+
     b, npnt, nq = 3, 9000, 3000
-    assert nat.lib().accv_polyline_grad_workspace_bytes(b, npnt, nq, 2, 0) >= b * npnt * 4 * 4
+    # 1024 threads, three chunks of 1024 queries: accumulators of 9000 * (2 + 2) floats per polyline and chunk, and the slab
+    plan = pc.plan(b, npnt, nq, 2, torch.float32)
+    assert plan.use_ws and (plan.threads, plan.chunks, plan.q_chunk) == (1024, 3, 1024)
+    assert plan.ws_acc == pc.align256(npnt * 4 * 4) * b * 3 and plan.ws_slab == pc.align256(3 * b * npnt * 2 * 4)
+    assert nat.lib().accv_polyline_grad_workspace_bytes(b, npnt, nq, 2, 0) == plan.ws_acc + plan.ws_slab
     p, fr = _lattice(b, npnt, nq, 2, True, seed=5, max_step=1)
     ps, qs = torch.tensor([9000, 4000, 1]), torch.tensor([3000, 2999, 17])
     gp, gd, rp, rd = _run(p, fr, True, torch.float32, ps, qs)
