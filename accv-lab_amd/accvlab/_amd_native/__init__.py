@@ -58,6 +58,13 @@ MB_IOU_NONE = 0
 MB_IOU = 1
 MB_GIOU = 2
 MB_MAX_D = 16
+PM_IDX_I64 = 1
+PM_REVERSIBLE = 2
+PM_LABELS_I64 = 4
+PM_CLOSED_I32 = 8
+PM_CLOSED_I64 = 16
+PM_MIN_P = 2
+PM_MAX_P = 128
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -140,6 +147,17 @@ SIGNATURES = {
     "accv_matched_box_loss_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
     "accv_matched_box_loss_bwd_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp,
                                             _vp]),
+    # polyline matching cost and matched polyline loss (params: a PolylineMatchParams by address; out of the loss is [2, B])
+    "accv_polyline_matching_cost": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
+    "accv_polyline_matching_cost_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp]),
+    "accv_matched_polyline_loss_workspace_bytes": (_sz, [_ll, _ll]),
+    "accv_matched_polyline_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _sz,
+                                        _vp]),
+    "accv_matched_polyline_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp,
+                                            _vp, _vp]),
+    "accv_matched_polyline_loss_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
+    "accv_matched_polyline_loss_bwd_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _ll, _ll, _ll, _ll, _ll, _ll,
+                                                 _vp, _vp]),
     # centre-point regression (maps: host arrays of pointers and channel counts; params: a CenterRegressionParams by address)
     "accv_gather_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
     "accv_scatter_at_centers": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp]),
@@ -195,6 +213,15 @@ class MatchedBoxParams(ctypes.Structure):
                 ("code_weights_dev", ctypes.c_void_p), ("query_weights", ctypes.c_void_p)]
 
 
+class PolylineMatchParams(ctypes.Structure):
+    """accv_polyline_match_params of include/accv_hip.h"""
+    _fields_ = ([(n, ctypes.c_double) for n in ("class_weight", "pts_weight", "focal_alpha", "focal_gamma", "focal_eps",
+                                                "filler", "dir_eps", "avg_factor")]
+                + [("pred_stride_b", ctypes.c_longlong), ("pred_stride_q", ctypes.c_longlong), ("class_kind", ctypes.c_int),
+                   ("avg_mode", ctypes.c_int), ("dir_loss", ctypes.c_int), ("avg_factor_dev", ctypes.c_void_p),
+                   ("gt_closed", ctypes.c_void_p)])
+
+
 class CenterRegressionParams(ctypes.Structure):
     """accv_center_regression_params of include/accv_hip.h"""
     _fields_ = [("kind", ctypes.c_int), ("avg_mode", ctypes.c_int), ("beta", ctypes.c_float), ("avg_factor", ctypes.c_float)]
@@ -216,7 +243,8 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
              "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
-             "accv_matched_box_loss_bwd_host"}
+             "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
+             "accv_matched_polyline_loss_bwd_host"}
 
 
 def _fast_entry(fn, res, args):

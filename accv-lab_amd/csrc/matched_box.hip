@@ -10,8 +10,8 @@
 // Forward: a workgroup owns kThreads consecutive queries of one frame.  It builds their query -> slot table in LDS
 // (atomicMin on the slot number in LDS; no global atomics); a lane per query looks its pair up, evaluates both terms and
 // the workgroup sums them in f64 in a fixed order: one (l1, iou) partial per workgroup in the caller's workspace.  A
-// one-block launch adds each frame's partials in a fixed order, counts the pairs, applies the denominator and leaves it
-// on the device for the backward.
+// one-block launch (matched_pair_finish.h) adds each frame's partials in a fixed order, counts the pairs, applies the
+// denominator and leaves it on the device for the backward.
 // Backward: the same table, then every element of the contiguous [B, Q, D] gradient written exactly once in the boxes'
 // dtype, +0 for a query without a pair: no zero fill, no atomics, no read of the gradient.  D == 4: a lane per query and
 // one store per row (16 bytes f32, 8 bytes f16 / bf16, 2 x 16 bytes f64) where the gradient's base allows it; other D: a
@@ -26,6 +26,7 @@
 
 #include "accv_common.h"
 #include "matched_box_arith.h"
+#include "matched_pair_finish.h"
 
 #pragma clang fp contract(off)
 
@@ -34,7 +35,6 @@ namespace {
 using namespace accv_mb;
 
 constexpr int kThreads = 256;               // and queries per workgroup
-constexpr int kFinishThreads = 1024;
 constexpr unsigned kKnownFlags = ACCV_MB_IDX_I64 | ACCV_MB_CXCYWH;
 constexpr int kNoSlot = INT_MAX;
 
@@ -176,44 +176,6 @@ __global__ __launch_bounds__(kThreads) void mb_fwd_kernel(const Args a, double* 
     if (threadIdx.x == 0) {
         part[blockIdx.x] = l1;
         part[(size_t)gridDim.x + blockIdx.x] = iou;
-    }
-}
-
-// one workgroup, a wave per frame: the frame's partials in a fixed order, the number of pairs, the denominator
-// (the scheme of mf_finish_kernel, for two sums); out is [2, B]
-template <class O>
-__global__ __launch_bounds__(kFinishThreads) void mb_finish_kernel(const double* __restrict__ part,
-                                                                   const long long* __restrict__ counts, long long B,
-                                                                   long long nqb, long long K, int avg_mode, double avg_value,
-                                                                   const float* __restrict__ avg_dev, O* __restrict__ out,
-                                                                   double* __restrict__ out_denom)
-{
-    __shared__ unsigned long long s_cnt[kFinishThreads / 64];
-    __shared__ double s_denom;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long m = 0;
-    if (avg_mode == ACCV_FL_AVG_NUM_POS)
-        for (long long b = threadIdx.x; b < B; b += kFinishThreads) m += (unsigned long long)clamp_count(counts, b, K, 1);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m += __shfl_xor(m, s);
-    if (lane == 0) s_cnt[wave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long total = 0;
-        for (int i = 0; i < kFinishThreads / 64; ++i) total += s_cnt[i];
-        const double denom = denominator(avg_mode, avg_value, avg_dev, total);
-        s_denom = denom;
-        *out_denom = denom;
-    }
-    __syncthreads();
-    const double denom = s_denom;
-    const long long blocks = B * nqb;
-    for (long long b = wave; b < B; b += kFinishThreads / 64) {
-        double l1 = 0.0, iou = 0.0;
-        for (long long i = lane; i < nqb; i += 64) l1 += part[b * nqb + i], iou += part[blocks + b * nqb + i];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) l1 += __shfl_xor(l1, s), iou += __shfl_xor(iou, s);
-        if (lane == 0) out[b] = (O)(l1 / denom), out[B + b] = (O)(iou / denom);
     }
 }
 
@@ -404,7 +366,7 @@ void launch_fwd(const Args& a, const accv_matched_box_params* p, double* part, v
 {
     using O = typename Compute<DT>::type;
     hipLaunchKernelGGL(mb_fwd_kernel<DT>, dim3((unsigned)(a.B * a.nqb)), dim3(kThreads), 0, s, a, part);
-    hipLaunchKernelGGL(mb_finish_kernel<O>, dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
+    hipLaunchKernelGGL(pair_finish_kernel<O>, dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
                        p->avg_factor, p->avg_factor_dev, static_cast<O*>(out), out_denom);
 }
 

@@ -593,6 +593,90 @@ int accv_matched_box_loss_bwd_host(const void* pred_boxes, const void* gt_boxes,
                                    long long stride_b, long long stride_q, const accv_matched_box_params* params,
                                    void* grad_boxes);
 
+/* --------------------------------------------------------------- polyline matching cost and matched polyline loss
+ * Set prediction over polylines (MapTR-style vectorised map heads, lane-DETR heads).  A line is P points of D coordinates
+ * (2 <= P <= 128, D 2 or 3); a ground-truth line equals all of its equivalent orders t^v:
+ *     open line     t^0[p] = t[p];  with ACCV_PM_REVERSIBLE also t^1[p] = t[P - 1 - p]
+ *     closed line   t^s[p] = t[(s + p) mod P], s < P;  with ACCV_PM_REVERSIBLE also t^(P + s)[p] = t[(s - p) mod P]
+ * gt_closed (params; NULL = every line is open) marks the closed lines: contiguous [B, G], non-zero = closed, one byte per
+ * element, or four / eight with ACCV_PM_CLOSED_I32 / ACCV_PM_CLOSED_I64.  v*(x, t) is the LOWEST v that minimises
+ * sum_{p, d} |x[p, d] - t^v[p, d]| in the arithmetic type (f32 for dtype 0 f32, 1 f16, 2 bf16, which are widened exactly;
+ * f64 for dtype 3); the sum runs over p, d in order in partial sums of 8 points.  No order is ever written to memory.
+ * pred_lines [B, Q, P, D]: element (b, q, p, d) at b * pred_stride_b + q * pred_stride_q + p * D + d (params; elements,
+ * pred_stride_q >= P * D); gt_lines: contiguous [B, G, P, D] of the same dtype.
+ *
+ * accv_polyline_matching_cost: out[b, q, g] (contiguous [B, Q, G], f32, f64 for dtype 3) is, for g < G_b =
+ * clamp(counts[b], 0, G) (counts: int64 [B], NULL = G for every frame),
+ *     class_weight * cls(q, l_g) + pts_weight * min_v sum_{p, d} |x_q - t_g^v|        (summed in this order)
+ * and params->filler for G_b <= g < G.  cls is the class term of accv_matching_cost (params->class_kind one of
+ * ACCV_MC_ONE_MINUS_PROB / _NEG_PROB / _FOCAL; scores [B, Q, C] with scores_stride_b / scores_stride_q, gt_labels [B, G]
+ * int32, int64 with ACCV_PM_LABELS_I64).  A term whose weight is 0 is not evaluated and its pointers may be NULL.  NaN
+ * in a coordinate of a pair gives NaN for that pair.  One launch, no host synchronisation; B * Q * G == 0 launches nothing.
+ *
+ * accv_matched_polyline_loss: over the pairs of accv_matched_box_loss (the same rule: slots j < clamp(counts[b], 0, K) of
+ * pred_ind / gt_ind [B, K], int32 or int64 with ACCV_PM_IDX_I64, the lowest slot that names a query with both indices in
+ * range is its pair), with t* = t_g^(v*):
+ *     out[0][b] = sum over the pairs of  sum_{p, d} |x[p, d] - t*[p, d]| / denom
+ *     out[1][b] = sum over the pairs of  sum_s (1 - <a_s, b_s> / sqrt((|a_s|^2 + dir_eps) (|b_s|^2 + dir_eps))) / denom
+ * a_s = x[s+1] - x[s], b_s = t*[s+1] - t*[s]; s = 0 .. P-2 for an open line, 0 .. P-1 with s + 1 mod P for a closed one;
+ * zeros, nothing evaluated, when params->dir_loss is 0.  denom as for accv_matched_focal_loss.  out [2, B] f32 (f64 for
+ * dtype 3), out_denom one f64 scalar for the backward, workspace accv_matched_polyline_loss_workspace_bytes(B, Q) bytes
+ * of device memory, 16-byte aligned.  Sums are accumulated in f64 in a fixed order: two launches, no atomics on global
+ * memory, no host synchronisation, bitwise reproducible.  B * Q == 0 launches nothing and writes nothing.
+ * accv_matched_polyline_loss_bwd: grad_lines (contiguous [B, Q, P, D], the lines' dtype) is written completely, every
+ * element exactly once, +0 for a query without a pair: s1 * sgn(x - t*) + s2 * d dir / d x with s1 = grad_pts[b] / *denom,
+ * s2 = grad_dir[b] / *denom formed in f64 and rounded to the arithmetic type (either may be NULL: zeros).  v* is a constant
+ * of the derivative and is searched again; sgn(0) = 0.  One launch, no atomics, no zero fill.
+ * All return ACCV_EINVAL (null params, negative size, unknown dtype / flag / class kind / avg mode, P outside [2, 128],
+ * D not 2 or 3, pred_stride_q < P * D, K above 2^31 - 1, null or misaligned pointers) or ACCV_EWORKSPACE before touching the
+ * device, ACCV_ELAUNCH if a launch fails.  The _host entries run the same operation sequence per pair on host memory and
+ * block the calling thread. */
+#define ACCV_PM_IDX_I64 1u
+#define ACCV_PM_REVERSIBLE 2u
+#define ACCV_PM_LABELS_I64 4u
+#define ACCV_PM_CLOSED_I32 8u
+#define ACCV_PM_CLOSED_I64 16u
+/* the scalar parameters and optional operands, host memory, read during the call */
+typedef struct accv_polyline_match_params {
+    double class_weight, pts_weight;                  /* cost */
+    double focal_alpha, focal_gamma, focal_eps, filler;
+    double dir_eps;                                   /* loss */
+    double avg_factor;                                /* the denominator of ACCV_FL_AVG_VALUE */
+    long long pred_stride_b, pred_stride_q;           /* strides of pred_lines, in elements */
+    int class_kind;                                   /* ACCV_MC_ONE_MINUS_PROB, ACCV_MC_NEG_PROB or ACCV_MC_FOCAL */
+    int avg_mode;                                     /* ACCV_FL_AVG_NUM_POS, ACCV_FL_AVG_VALUE or ACCV_FL_AVG_DEVICE */
+    int dir_loss;                                     /* 0: the direction term is not evaluated */
+    const float* avg_factor_dev;                      /* the f32 scalar of ACCV_FL_AVG_DEVICE */
+    const void* gt_closed;                            /* NULL or [B, G] */
+} accv_polyline_match_params;
+int accv_polyline_matching_cost(const void* pred_lines, const void* gt_lines, const void* scores, const void* gt_labels,
+                                const long long* counts, int dtype, unsigned flags, long long B, long long Q, long long G,
+                                long long P, long long D, long long C, long long scores_stride_b, long long scores_stride_q,
+                                const accv_polyline_match_params* params, void* out, void* stream);
+int accv_polyline_matching_cost_host(const void* pred_lines, const void* gt_lines, const void* scores, const void* gt_labels,
+                                     const long long* counts, int dtype, unsigned flags, long long B, long long Q,
+                                     long long G, long long P, long long D, long long C, long long scores_stride_b,
+                                     long long scores_stride_q, const accv_polyline_match_params* params, void* out);
+size_t accv_matched_polyline_loss_workspace_bytes(long long B, long long Q);
+int accv_matched_polyline_loss(const void* pred_lines, const void* gt_lines, const void* pred_ind, const void* gt_ind,
+                               const long long* counts, int dtype, unsigned flags, long long B, long long Q, long long G,
+                               long long P, long long D, long long K, const accv_polyline_match_params* params, void* out,
+                               double* out_denom, void* workspace, size_t workspace_bytes, void* stream);
+int accv_matched_polyline_loss_bwd(const void* pred_lines, const void* gt_lines, const void* pred_ind, const void* gt_ind,
+                                   const long long* counts, const void* grad_pts, const void* grad_dir, const double* denom,
+                                   int dtype, unsigned flags, long long B, long long Q, long long G, long long P,
+                                   long long D, long long K, const accv_polyline_match_params* params, void* grad_lines,
+                                   void* stream);
+int accv_matched_polyline_loss_host(const void* pred_lines, const void* gt_lines, const void* pred_ind, const void* gt_ind,
+                                    const long long* counts, int dtype, unsigned flags, long long B, long long Q,
+                                    long long G, long long P, long long D, long long K,
+                                    const accv_polyline_match_params* params, void* out, double* out_denom);
+int accv_matched_polyline_loss_bwd_host(const void* pred_lines, const void* gt_lines, const void* pred_ind,
+                                        const void* gt_ind, const long long* counts, const void* grad_pts,
+                                        const void* grad_dir, const double* denom, int dtype, unsigned flags, long long B,
+                                        long long Q, long long G, long long P, long long D, long long K,
+                                        const accv_polyline_match_params* params, void* grad_lines);
+
 /* combine_data / split on device (batched_processing_py.py:410-423, ragged_batch.py:870-934):
  * unpack == 0: padded[i, j, :] = flat[offsets[i] + j, :] for j < sizes[i], zero bytes elsewhere;
  * unpack != 0: the inverse copy (flat <- padded, valid entries only).  offsets/sizes are device int64. */
