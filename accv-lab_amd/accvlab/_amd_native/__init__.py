@@ -65,6 +65,11 @@ PM_CLOSED_I32 = 8
 PM_CLOSED_I64 = 16
 PM_MIN_P = 2
 PM_MAX_P = 128
+CT_MAX_TASKS = 8
+CT_MAX_CLASSES = 64
+CT_NO_TASK = 255
+CT_LABELS_I64 = 1
+CT_COUNTS_I64 = 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -166,6 +171,11 @@ SIGNATURES = {
                                          _sz, _vp]),
     "accv_center_regression_loss_bwd": (_i, [_vp, _vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp, _ll, _u, _vp, _vp, _vp, _vp, _vp,
                                              _vp]),
+    # centre-point targets from ragged 3D boxes (params: a CenterPointTargetsParams by address; outputs [T, B, M, ...])
+    "accv_center_point_targets": (_i, [_vp, _vp, _vp, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp]),
+    "accv_center_point_targets_host": (_i, [_vp, _vp, _vp, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -227,6 +237,14 @@ class CenterRegressionParams(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("avg_mode", ctypes.c_int), ("beta", ctypes.c_float), ("avg_factor", ctypes.c_float)]
 
 
+class CenterPointTargetsParams(ctypes.Structure):
+    """accv_center_point_targets_params of include/accv_hip.h"""
+    _fields_ = [("pc_range", ctypes.c_double * 2), ("voxel_size", ctypes.c_double * 2), ("out_size_factor", ctypes.c_double),
+                ("gaussian_overlap", ctypes.c_double), ("min_radius", ctypes.c_int), ("max_objs", ctypes.c_int),
+                ("norm_bbox", ctypes.c_int), ("num_tasks", ctypes.c_int), ("class_task", ctypes.c_ubyte * 64),
+                ("class_pos", ctypes.c_ubyte * 64)]
+
+
 _lib = None
 _handle = None
 
@@ -244,7 +262,7 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
-             "accv_matched_polyline_loss_bwd_host"}
+             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host"}
 
 
 def _fast_entry(fn, res, args):

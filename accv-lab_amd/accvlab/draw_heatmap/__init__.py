@@ -11,9 +11,12 @@ launch), ``draw_targets_multiscale`` (box maps + lane maps of a step in two laun
 ``gaussian_focal_loss`` (the fused GaussianFocalLoss centerness term, forward and backward), and their read-back
 ``heatmap_peaks`` (local-maximum suppression + top-k in two launches, with a defined tie order), and the regression branch
 of the same heads: ``gather_at_centers`` (the maps' values at the object centres or at the peaks' indices) and
-``center_regression_loss`` (their L1 / smooth-L1 loss; the backward of both writes the gradient maps in one pass).
+``center_regression_loss`` (their L1 / smooth-L1 loss; the backward of both writes the gradient maps in one pass), and the
+front of that path: ``center_point_targets`` (raw ragged 3D boxes -> centres, radii, in-task labels, regression targets and
+indices of every task of a CenterPoint head in one launch).
 """
 from .center_regression import center_regression_loss, gather_at_centers
+from .center_targets import CenterPointTargets, center_point_targets
 from .focal_loss import gaussian_focal_loss
 from .lanes import (draw_polylines_batched, draw_polylines_multiscale, draw_targets_multiscale, sample_lane_targets,
                     sample_lanes)
@@ -23,4 +26,5 @@ from .peaks import HeatmapPeaks, heatmap_peaks
 __version__ = "0.1.0"
 __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_and_radii", "draw_polylines_batched",
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
-           "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss"]
+           "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
+           "center_point_targets", "CenterPointTargets"]

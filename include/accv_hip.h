@@ -395,6 +395,59 @@ int accv_center_regression_loss_bwd(const void* const* maps, void* const* grad_m
                                     const float* weights_or_null, const accv_center_regression_params* params,
                                     const float* grad_out, const float* denom, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ centre-point targets
+ * The target side of a centre-point head (mmdet3d's CenterHead.get_targets_single) for a ragged batch of 3D boxes and
+ * every task of the head in ONE launch: integer centres, Gaussian radii, in-task labels, regression targets, in-plane
+ * indices and the source slot of every kept object, compacted per (task, frame) in ascending slot order.
+ *
+ * boxes: f32 [B, N, D] contiguous, D = 7 or 9 as (x, y, z, dx, dy, dz, yaw[, vx, vy]); labels [B, N] int32 (int64 with
+ * ACCV_CT_LABELS_I64); counts [B] int32 (int64 with ACCV_CT_COUNTS_I64), clamped to [0, N]: only slots below it are read.
+ * params->class_task[c] is the task of class c (ACCV_CT_NO_TASK: none) and class_pos[c] its position inside that task; a
+ * label outside [0, ACCV_CT_MAX_CLASSES) belongs to no task.  Per frame b and task t, in float32 (the operation sequence
+ * is written out in csrc/center_targets_arith.h: correctly rounded division (__fdiv_rn) and square root (sqrtf under
+ * hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt), nothing contracted):
+ *   candidates  the slots n < counts[b] whose label is in task t, ascending; only the first max_objs of them go on
+ *   kept        w = dx / vs0 / f > 0, l = dy / vs1 / f > 0, cx = (x - pc0) / vs0 / f in (-1, W), cy likewise in (-1, H);
+ *               NaN fails; cell = ((int)cx, (int)cy), truncated toward zero
+ *   radius      max(min_radius, (int)gaussian_radius((l, w), gaussian_overlap)) (CenterPoint's three-root rule; a NaN
+ *               root converts to 0, the conversion saturates)
+ *   target      (cx - cell_x, cy - cell_y, z, dims, sin yaw, cos yaw[, vx, vy]), D + 1 channels; dims = log(dx, dy, dz)
+ *               with norm_bbox, else raw
+ * Outputs, [T, B, M, ...] contiguous with M >= min(max_objs, N): centers int32 (x, y), radii int32, out_labels int32,
+ * targets f32 [.., D + 1], indices int64 (y * W + x), source int32 (the slot n), out_sizes int64 [T, B] (kept count).
+ * Slots kept .. M-1 are written too: 0 everywhere, source -1 (a complete write).  One workgroup per (frame, task), no
+ * atomics, no host synchronisation, bitwise reproducible.  B == 0 or M == 0 launches nothing and writes nothing.
+ * Returns ACCV_EINVAL (null params, negative size, T outside 1..ACCV_CT_MAX_TASKS, D not 7 / 9, unknown flags, a class of
+ * task >= T, non-positive voxel size / out_size_factor, W or H < 1 or W * H >= 2^31, N above 2^31 - 1, M below
+ * min(max_objs, N), null or misaligned pointers) before touching the device, ACCV_ELAUNCH if the launch fails.
+ * accv_center_point_targets_host runs the same operation sequence serially on host memory. */
+#define ACCV_CT_MAX_TASKS 8
+#define ACCV_CT_MAX_CLASSES 64
+#define ACCV_CT_NO_TASK 255
+#define ACCV_CT_LABELS_I64 1u
+#define ACCV_CT_COUNTS_I64 2u
+/* the scalar parameters and the class table, host memory, read during the call */
+typedef struct accv_center_point_targets_params {
+    double pc_range[2];        /* x, y of the range's lower corner */
+    double voxel_size[2];      /* x, y; > 0 */
+    double out_size_factor;    /* > 0 */
+    double gaussian_overlap;
+    int min_radius;
+    int max_objs;              /* >= 0 */
+    int norm_bbox;
+    int num_tasks;             /* T */
+    unsigned char class_task[ACCV_CT_MAX_CLASSES];
+    unsigned char class_pos[ACCV_CT_MAX_CLASSES];
+} accv_center_point_targets_params;
+int accv_center_point_targets(const float* boxes, const void* labels, const void* counts, unsigned flags, long long B,
+                              long long N, long long D, long long W, long long H, long long M,
+                              const accv_center_point_targets_params* params, int* centers, int* radii, int* out_labels,
+                              float* targets, long long* indices, int* source, long long* out_sizes, void* stream);
+int accv_center_point_targets_host(const float* boxes, const void* labels, const void* counts, unsigned flags, long long B,
+                                   long long N, long long D, long long W, long long H, long long M,
+                                   const accv_center_point_targets_params* params, int* centers, int* radii,
+                                   int* out_labels, float* targets, long long* indices, int* source, long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
