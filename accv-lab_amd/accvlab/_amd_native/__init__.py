@@ -70,6 +70,10 @@ CT_MAX_CLASSES = 64
 CT_NO_TASK = 255
 CT_LABELS_I64 = 1
 CT_COUNTS_I64 = 2
+CD_MAX_TASKS = 8
+CD_MAX_MAPS = 8
+CD_MAX_CLASSES = 64
+CD_MAX_K = 1024
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -176,6 +180,9 @@ SIGNATURES = {
                                        _vp]),
     "accv_center_point_targets_host": (_i, [_vp, _vp, _vp, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
+    # centre-point decoding with circle NMS (params: a CenterPointDecodeParams by address; outputs [T, B, M, ...])
+    "accv_center_point_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_center_point_decode_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -245,6 +252,18 @@ class CenterPointTargetsParams(ctypes.Structure):
                 ("class_pos", ctypes.c_ubyte * 64)]
 
 
+class CenterPointDecodeParams(ctypes.Structure):
+    """accv_center_point_decode_params of include/accv_hip.h"""
+    _fields_ = [("scores", ctypes.c_void_p * 8), ("indices", ctypes.c_void_p * 8), ("classes", ctypes.c_void_p * 8),
+                ("maps", (ctypes.c_void_p * 8) * 8), ("channels", (ctypes.c_int * 8) * 8), ("num_maps", ctypes.c_int * 8),
+                ("has_nms", ctypes.c_int * 8), ("nms_threshold", ctypes.c_double * 8), ("pc_range", ctypes.c_double * 2),
+                ("voxel_size", ctypes.c_double * 2), ("out_size_factor", ctypes.c_double), ("score_threshold", ctypes.c_double),
+                ("post_center_range", ctypes.c_double * 6), ("score_dtype", ctypes.c_int), ("map_dtype", ctypes.c_int),
+                ("num_tasks", ctypes.c_int), ("has_score_threshold", ctypes.c_int), ("has_post_center_range", ctypes.c_int),
+                ("scores_are_logits", ctypes.c_int), ("norm_bbox", ctypes.c_int), ("bottom_center", ctypes.c_int),
+                ("task_first", ctypes.c_ubyte * 9), ("class_ids", ctypes.c_ubyte * 64)]
+
+
 _lib = None
 _handle = None
 
@@ -262,7 +281,7 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
-             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host"}
+             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host"}
 
 
 def _fast_entry(fn, res, args):

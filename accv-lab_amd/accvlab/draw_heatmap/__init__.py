@@ -13,8 +13,11 @@ launch), ``draw_targets_multiscale`` (box maps + lane maps of a step in two laun
 of the same heads: ``gather_at_centers`` (the maps' values at the object centres or at the peaks' indices) and
 ``center_regression_loss`` (their L1 / smooth-L1 loss; the backward of both writes the gradient maps in one pass), and the
 front of that path: ``center_point_targets`` (raw ragged 3D boxes -> centres, radii, in-task labels, regression targets and
-indices of every task of a CenterPoint head in one launch).
+indices of every task of a CenterPoint head in one launch), and its inverse at the end of the path:
+``center_point_decode`` (the peaks and regression maps of every task -> filtered, circle-NMS'd, compacted boxes, scores
+and labels in one launch).
 """
+from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
 from .center_targets import CenterPointTargets, center_point_targets
 from .focal_loss import gaussian_focal_loss
@@ -27,4 +30,4 @@ __version__ = "0.1.0"
 __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_and_radii", "draw_polylines_batched",
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
            "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
-           "center_point_targets", "CenterPointTargets"]
+           "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections"]

@@ -448,6 +448,72 @@ int accv_center_point_targets_host(const float* boxes, const void* labels, const
                                    const accv_center_point_targets_params* params, int* centers, int* radii,
                                    int* out_labels, float* targets, long long* indices, int* source, long long* out_sizes);
 
+/* ------------------------------------------------------------------------------------------------ centre-point decoding
+ * The prediction side of a centre-point head, the inverse of accv_center_point_targets: mmdet3d's
+ * CenterPointBBoxCoder.decode (core/bbox/coders/centerpoint_bbox_coders.py: the gathers, exp, atan2, the affine map back
+ * to metres, the score and post_center_range masks and the boolean index per frame) and the `circle` branch of
+ * CenterHead.get_bboxes (models/dense_heads/centerpoint_head.py: circle_nms, a numba loop on the host, and the
+ * post_max_size cut) for every task of the head in ONE launch, without a host round trip.
+ *
+ * Per task t: the peaks scores[t] [B, K] (dtype score_dtype: 0 f32, 1 f16, 2 bf16), indices[t] and classes[t] int64
+ * [B, K] (what accv_heatmap_peaks writes with per_class == 0), 1 <= K <= ACCV_CD_MAX_K, in rank order; and num_maps[t]
+ * (1..ACCV_CD_MAX_MAPS) maps [B, channels[t][i], H, W] contiguous of dtype map_dtype, read in place, whose channels
+ * concatenate to C = 8 or 10 (the same for every task): (off_x, off_y, z, d0, d1, d2, sin, cos[, vx, vy]).
+ * class_ids holds the global class ids of task 0, then of task 1, ...; task t owns class_ids[task_first[t] ..
+ * task_first[t + 1]), so classes[t][b, k] is a position below task_first[t + 1] - task_first[t].
+ * Per (b, t, k), in float32 (the operation sequence is written out in csrc/center_decode_arith.h, nothing contracted):
+ *   legal     0 <= index < H * W and 0 <= class position < the task's class count; nothing is read for an illegal peak
+ *   centre    x = ((index % W + off_x) * out_size_factor) * voxel_size[0] + pc_range[0], y likewise from index / W
+ *   score     scores[b, k], or 1 / (1 + exp(-scores[b, k])) with scores_are_logits
+ *   valid     legal && (no threshold || score > score_threshold) && (no range || post_center_range[0:3] <= (x, y, z) <=
+ *             post_center_range[3:6]); NaN fails
+ *   circle    with has_nms[t]: in rank order a valid peak is kept iff no earlier kept peak j has
+ *             (x - xj)^2 + (y - yj)^2 <= nms_threshold[t] (the squared distance against the threshold as given, mmdet3d's
+ *             rule); class-agnostic inside the task; a NaN distance suppresses nothing
+ *   written   the first M kept peaks in rank order: boxes row (x, y, z, dims, atan2(sin, cos)[, vx, vy]), dims = exp(d)
+ *             with norm_bbox, z - dims[2] * 0.5 with bottom_center (after the range test); the score; the global class id;
+ *             source = k
+ * Outputs, [T, B, M, ...] contiguous with 1 <= M <= K: boxes f32 [.., C - 1], out_scores f32, labels int64, source int32,
+ * out_sizes int64 [T, B] (min(kept, M)).  Slots from out_sizes on are written too: +0 everywhere, source -1 (a complete
+ * write).  One workgroup per (frame, task), no atomics, no workspace, no host synchronisation, bitwise reproducible.
+ * B == 0 launches nothing and writes nothing.  Returns ACCV_EINVAL (null params, negative size, T outside
+ * 1..ACCV_CD_MAX_TASKS, K outside 1..ACCV_CD_MAX_K, M outside 1..K, a map count outside 1..ACCV_CD_MAX_MAPS, channels that
+ * do not add up to the same 8 or 10 for every task, an unknown dtype, an inconsistent class table, non-positive voxel
+ * size / out_size_factor, NaN in a threshold or range, W or H < 1 or W * H >= 2^31, null or misaligned pointers) before
+ * touching the device, ACCV_ELAUNCH if the launch fails.
+ * accv_center_point_decode_host runs the same operation sequence serially on host memory. */
+#define ACCV_CD_MAX_TASKS 8
+#define ACCV_CD_MAX_MAPS 8
+#define ACCV_CD_MAX_CLASSES 64
+#define ACCV_CD_MAX_K 1024
+/* the per-task pointers, the scalar parameters and the class table: host memory, read during the call */
+typedef struct accv_center_point_decode_params {
+    const void* scores[ACCV_CD_MAX_TASKS];
+    const long long* indices[ACCV_CD_MAX_TASKS];
+    const long long* classes[ACCV_CD_MAX_TASKS];
+    const void* maps[ACCV_CD_MAX_TASKS][ACCV_CD_MAX_MAPS];
+    int channels[ACCV_CD_MAX_TASKS][ACCV_CD_MAX_MAPS];
+    int num_maps[ACCV_CD_MAX_TASKS];
+    int has_nms[ACCV_CD_MAX_TASKS];
+    double nms_threshold[ACCV_CD_MAX_TASKS];
+    double pc_range[2];             /* x, y of the range's lower corner */
+    double voxel_size[2];           /* x, y; > 0 */
+    double out_size_factor;         /* > 0 */
+    double score_threshold;
+    double post_center_range[6];
+    int score_dtype, map_dtype;     /* 0 f32, 1 f16, 2 bf16 */
+    int num_tasks;                  /* T */
+    int has_score_threshold, has_post_center_range, scores_are_logits, norm_bbox, bottom_center;
+    unsigned char task_first[ACCV_CD_MAX_TASKS + 1];
+    unsigned char class_ids[ACCV_CD_MAX_CLASSES];
+} accv_center_point_decode_params;
+int accv_center_point_decode(const accv_center_point_decode_params* params, long long B, long long K, long long H,
+                             long long W, long long M, float* boxes, float* out_scores, long long* labels, int* source,
+                             long long* out_sizes, void* stream);
+int accv_center_point_decode_host(const accv_center_point_decode_params* params, long long B, long long K, long long H,
+                                  long long W, long long M, float* boxes, float* out_scores, long long* labels, int* source,
+                                  long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
