@@ -74,6 +74,10 @@ CD_MAX_TASKS = 8
 CD_MAX_MAPS = 8
 CD_MAX_CLASSES = 64
 CD_MAX_K = 1024
+RN_MAX_TASKS = 8
+RN_MAX_N = 1024
+RN_MIN_D = 7
+RN_MAX_D = 16
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -183,6 +187,11 @@ SIGNATURES = {
     # centre-point decoding with circle NMS (params: a CenterPointDecodeParams by address; outputs [T, B, M, ...])
     "accv_center_point_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_center_point_decode_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+    # rotated BEV IoU and rotated NMS (params: a RotatedNmsParams by address; NMS outputs [T, B, M, ...])
+    "accv_rotated_iou_bev": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp]),
+    "accv_rotated_iou_bev_host": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp]),
+    "accv_rotated_nms_bev": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_rotated_nms_bev_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -264,6 +273,13 @@ class CenterPointDecodeParams(ctypes.Structure):
                 ("task_first", ctypes.c_ubyte * 9), ("class_ids", ctypes.c_ubyte * 64)]
 
 
+class RotatedNmsParams(ctypes.Structure):
+    """accv_rotated_nms_params of include/accv_hip.h"""
+    _fields_ = [("boxes", ctypes.c_void_p * 8), ("scores", ctypes.c_void_p * 8), ("labels", ctypes.c_void_p * 8),
+                ("source", ctypes.c_void_p * 8), ("sizes", ctypes.c_void_p * 8), ("iou_threshold", ctypes.c_double * 8),
+                ("has_threshold", ctypes.c_int * 8), ("num_tasks", ctypes.c_int)]
+
+
 _lib = None
 _handle = None
 
@@ -281,7 +297,8 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
-             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host"}
+             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host",
+             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host"}
 
 
 def _fast_entry(fn, res, args):

@@ -15,7 +15,8 @@ of the same heads: ``gather_at_centers`` (the maps' values at the object centres
 front of that path: ``center_point_targets`` (raw ragged 3D boxes -> centres, radii, in-task labels, regression targets and
 indices of every task of a CenterPoint head in one launch), and its inverse at the end of the path:
 ``center_point_decode`` (the peaks and regression maps of every task -> filtered, circle-NMS'd, compacted boxes, scores
-and labels in one launch).
+and labels in one launch), and the other NMS of those heads after it: ``rotated_nms_bev`` (rotated BEV-IoU NMS of every
+task's detections in one launch) over ``rotated_iou_bev`` (the pairwise rotated IoU of two ragged BEV box sets).
 """
 from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
@@ -25,9 +26,11 @@ from .lanes import (draw_polylines_batched, draw_polylines_multiscale, draw_targ
                     sample_lanes)
 from .ops import draw_heatmap, draw_heatmap_batched, draw_heatmap_multiscale, get_centers_and_radii
 from .peaks import HeatmapPeaks, heatmap_peaks
+from .rotated_nms import rotated_iou_bev, rotated_nms_bev
 
 __version__ = "0.1.0"
 __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_and_radii", "draw_polylines_batched",
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
            "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
-           "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections"]
+           "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
+           "rotated_nms_bev"]

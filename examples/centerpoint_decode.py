@@ -8,10 +8,15 @@ after mmdet3d's CenterPointBBoxCoder.decode and the `circle` branch of CenterHea
 gathers, exp / atan2 / the affine map, two masks, and per frame a boolean index, the centres to the host, the circle NMS
 there and the kept indices back.  Both print the same detections.
 
-    python3 examples/centerpoint_decode.py
+    python3 examples/centerpoint_decode.py [--nms {circle,rotate}]
+
+`--nms rotate` shows the other branch of CenterHead.get_bboxes: the decode runs without NMS and `rotated_nms_bev` (rotated
+BEV-IoU NMS, mmdet3d's nms_bev over mmcv's nms_rotated) follows it, again for every task in one launch and without a host
+round trip; it is compared with the library's own host entry on a copy of the decode's output.
 """
 from __future__ import annotations
 
+import argparse
 import math
 import os
 import sys
@@ -21,12 +26,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np
 import torch
 
-from accvlab.draw_heatmap import center_point_decode, gather_at_centers, heatmap_peaks
+from accvlab.batching_helpers import RaggedBatch
+from accvlab.draw_heatmap import CenterPointDetections, center_point_decode, gather_at_centers, heatmap_peaks, rotated_nms_bev
 
 TASKS = ((0,), (1, 2), (3, 4), (5,), (6, 7), (8, 9))            # the six nuScenes tasks over ten classes
 MIN_RADIUS = [4, 12, 10, 1, 0.85, 0.175]                        # mmdet3d's nuScenes test_cfg
 CFG = dict(pc_range=[-51.2, -51.2], voxel_size=[0.2, 0.2], out_size_factor=4)
 TEST = dict(score_threshold=0.1, post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], nms_threshold=MIN_RADIUS, post_max_size=83)
+ROTATE = dict(iou_threshold=0.2, pre_max_size=1000, post_max_size=83)   # mmdet3d's nuScenes test_cfg of the `rotate` branch
 H = W = 128
 K = 500
 
@@ -48,6 +55,14 @@ def make_heads(batch: int, device, seed: int = 1):
 def fused_decode(logits, heads):
     peaks = [heatmap_peaks(lg, K, kernel=1) for lg in logits]                 # ranks the logits: sigmoid is monotone
     return peaks, center_point_decode(peaks, heads, TASKS, **CFG, scores_are_logits=True, **TEST)
+
+
+def rotate_decode(logits, heads):
+    """the `rotate` branch: the decode without NMS, then the rotated NMS of every task in one launch"""
+    peaks = [heatmap_peaks(lg, K, kernel=1) for lg in logits]
+    test = dict(TEST, nms_threshold=None, post_max_size=None)
+    dets = center_point_decode(peaks, heads, TASKS, **CFG, scores_are_logits=True, **test)
+    return peaks, dets, rotated_nms_bev(dets, ROTATE["iou_threshold"], pre_max_size=ROTATE["pre_max_size"], post_max_size=ROTATE["post_max_size"])
 
 
 def circle_nms(xy, thresh, post_max_size):
@@ -87,11 +102,35 @@ def composed_decode(logits, heads):
     return out
 
 
+def main_rotate(logits, heads):
+    peaks, before, dets = rotate_decode(logits, heads)
+    on_host = []                                                                       # the same operator on host copies
+    for d in before:
+        sizes = d.boxes.sample_sizes.cpu()
+        on_host.append(CenterPointDetections(*(RaggedBatch(x.tensor.cpu(), sample_sizes=sizes) for x in d)))
+    ref = rotated_nms_bev(on_host, ROTATE["iou_threshold"], pre_max_size=ROTATE["pre_max_size"], post_max_size=ROTATE["post_max_size"])
+    for t, (d, r, b4) in enumerate(zip(dets, ref, before)):
+        for b in range(d.boxes.tensor.shape[0]):
+            n = int(d.boxes.sample_sizes[b])
+            same = n == int(r.boxes.sample_sizes[b]) and torch.equal(d.source.tensor[b].cpu(), r.source.tensor[b])
+            print(f"task {t} frame {b}: {int(b4.boxes.sample_sizes[b])} decoded, {n} after rotated NMS, equal to the host entry {same}, "
+                  f"best score {float(d.scores.tensor[b, 0]):.3f} from peak rank {int(d.source.tensor[b, 0])}")
+    d = dets[0]
+    cells = peaks[0].indices.gather(1, d.source.tensor.clamp(min=0).long())
+    rows = gather_at_centers(heads[0], cells)
+    print("rows of task 0 for a loss on the detections:", tuple(rows.shape))
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nms", choices=("circle", "rotate"), default="circle")
+    args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("this example runs heatmap_peaks, which needs a GPU")
     dev = torch.device("cuda", 0)
     logits, heads = make_heads(2, dev)
+    if args.nms == "rotate":
+        return main_rotate(logits, heads)
     peaks, dets = fused_decode(logits, heads)
     ref = composed_decode(logits, heads)
     for t, (d, frames) in enumerate(zip(dets, ref)):

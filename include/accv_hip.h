@@ -514,6 +514,56 @@ int accv_center_point_decode_host(const accv_center_point_decode_params* params,
                                   long long W, long long M, float* boxes, float* out_scores, long long* labels, int* source,
                                   long long* out_sizes);
 
+/* ------------------------------------------------------------------------------------- rotated BEV IoU and rotated NMS
+ * The `rotate` branch of mmdet3d's CenterHead.get_bboxes (nms_bev over mmcv's nms_rotated) and the IoU underneath it
+ * (mmcv's box_iou_rotated), on the device, ragged, for every task in one launch.  A BEV box is (x, y, dx, dy, yaw).  The
+ * float32 operation sequence is written out in csrc/rotated_iou_arith.h: A is moved into B's frame, its corner polygon is
+ * clipped (Sutherland-Hodgman) against B's four axis-aligned half-planes, the area is the shoelace sum relative to the first
+ * vertex, iou = inter / (dxA * dyA + dxB * dyB - inter).  A box whose five values are not all finite, or with dx <= 0 or
+ * dy <= 0, has IoU +0 with every box; boxes whose circumscribed circles are apart have IoU +0 (an exact reject).
+ *
+ * accv_rotated_iou_bev: a [B, Na, 5] and b [B, Nb, 5] float32 contiguous with int64 sizes [B] each (clamped to [0, Na] /
+ * [0, Nb]); out [B, Na, Nb] float32, out[f, i, j] = IoU of a[f, i] against b[f, j], +0 where i or j is beyond its size;
+ * every element is written exactly once.  B, Na or Nb == 0 launches nothing.
+ *
+ * accv_rotated_nms_bev: per task t the inputs boxes[t] [B, N, D] f32 (BEV columns 0, 1, 3, 4, 6), scores[t] [B, N] f32,
+ * labels[t] [B, N] int64, source[t] [B, N] int32 and sizes[t] [B] int64: what accv_center_point_decode writes without NMS.
+ * Per (b, t) only the first n = min(sizes[t][b], pre_max_size) slots exist, and the slot order is the priority order
+ * (nothing is sorted).  With has_threshold[t]: walking the slots in order, a box is kept iff no earlier kept box has
+ * iou > iou_threshold[t] with it (strictly: mmcv's rule); a box that is not ok is kept and suppresses nothing.  Without: every
+ * slot is kept.  The first M kept rows go to output slots 0 .. in slot order, all D columns, score, label and source bit for
+ * bit.  Outputs, [T, B, M, ...] contiguous with 1 <= M <= min(N, pre_max_size): boxes f32 [.., D], scores f32, labels int64,
+ * source int32, out_sizes int64 [T, B] (min(kept, M)); slots from out_sizes on are written too: +0 everywhere, source -1.
+ * One workgroup per (frame, task), no atomics, no workspace, no host synchronisation, bitwise reproducible.  B == 0 launches
+ * nothing.  Limits: 1 <= T <= ACCV_RN_MAX_TASKS, 1 <= N <= ACCV_RN_MAX_N, ACCV_RN_MIN_D <= D <= ACCV_RN_MAX_D.
+ * Both return ACCV_EINVAL (negative or oversized extent, a NaN threshold, null or misaligned pointers) before touching the
+ * data, ACCV_ELAUNCH if the launch fails.  The _host entries run the same operation sequence serially on host memory. */
+#define ACCV_RN_MAX_TASKS 8
+#define ACCV_RN_MAX_N 1024
+#define ACCV_RN_MIN_D 7
+#define ACCV_RN_MAX_D 16
+/* the per-task pointers and thresholds: host memory, read during the call */
+typedef struct accv_rotated_nms_params {
+    const float* boxes[ACCV_RN_MAX_TASKS];
+    const float* scores[ACCV_RN_MAX_TASKS];
+    const long long* labels[ACCV_RN_MAX_TASKS];
+    const int* source[ACCV_RN_MAX_TASKS];
+    const long long* sizes[ACCV_RN_MAX_TASKS];
+    double iou_threshold[ACCV_RN_MAX_TASKS];
+    int has_threshold[ACCV_RN_MAX_TASKS];
+    int num_tasks;                  /* T */
+} accv_rotated_nms_params;
+int accv_rotated_iou_bev(const float* a, const long long* a_sizes, const float* b, const long long* b_sizes, long long B,
+                         long long Na, long long Nb, float* out, void* stream);
+int accv_rotated_iou_bev_host(const float* a, const long long* a_sizes, const float* b, const long long* b_sizes, long long B,
+                              long long Na, long long Nb, float* out);
+int accv_rotated_nms_bev(const accv_rotated_nms_params* params, long long B, long long N, long long D, long long pre_max_size,
+                         long long M, float* boxes, float* scores, long long* labels, int* source, long long* out_sizes,
+                         void* stream);
+int accv_rotated_nms_bev_host(const accv_rotated_nms_params* params, long long B, long long N, long long D,
+                              long long pre_max_size, long long M, float* boxes, float* scores, long long* labels, int* source,
+                              long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
