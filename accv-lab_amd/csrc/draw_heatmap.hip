@@ -70,6 +70,11 @@ struct SplatParams {
     // point splats (SRC == 2): centers_f = sampled points [B, n_max, 2]; boxes_f = bounding boxes of every 64 consecutive
     // points [B, n_groups, 4] (xmin, ymin, xmax, ymax; source pixels); every point gets the same radius
     int radius, n_groups;
+#ifdef ACCV_SPLAT_STAMPS
+    // diagnostic build only (scripts/splat_phase_stamps.py): one 64-byte record of phase time stamps per tile wave
+    unsigned long long* stamps;
+    long long stamp_records;
+#endif
 };
 
 constexpr int kMaxScales = 4;
@@ -302,6 +307,22 @@ __device__ __forceinline__ float max3_skip_nan(float acc, float a, float b)
     return r;
 }
 
+#ifdef ACCV_SPLAT_STAMPS
+__device__ __forceinline__ unsigned long long phase_stamp()   // 100 MHz constant clock; pinned in program order
+{
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long v = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_sched_barrier(0);
+    return v;
+}
+__device__ __forceinline__ unsigned xcc_id()
+{
+    unsigned v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(v));
+    return v;
+}
+#endif
+
 template <int PX, int R, bool CLEAR, int SM, int WPG, int SRC>
 __device__ __forceinline__ void splat_body(const SplatParams& p, long long linear_group)
 {
@@ -313,6 +334,18 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
     __shared__ Hit s_hit[kWavesPerGroup][kCand];
     __shared__ __attribute__((aligned(16))) float s_ey[kWavesPerGroup][kCand][TH];
 
+    // fused-clear tile kernel: the half-waves share a hit's column factors (see the accumulate loop).  Not the in-place
+    // instantiations (register bound) and not the multi-scale launches
+    constexpr bool kSharedColumns = CLEAR && SRC == 0 && PX == 4;
+#ifdef ACCV_SPLAT_STAMPS
+    // a stamp after each cull round, after each row table and after each accumulate loop; the record holds the wave's start,
+    // the time it spent in each of the three kinds of phase (summed over its rounds), the end of its last phase before the
+    // stores and the time after its last store was issued
+    constexpr bool kStamps = CLEAR && SRC == 0 && PX == 4;
+    unsigned long long st_start = 0, st_prev = 0, st_cull = 0, st_table = 0, st_acc = 0;
+    int rounds = 0;
+    if constexpr (kStamps) st_start = st_prev = phase_stamp();
+#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     TileCtx t;
@@ -343,6 +376,14 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
         }
         const bool hit = (m >> lane) & 1ull;
         const int nh = __popcll(m);
+#ifdef ACCV_SPLAT_STAMPS
+        if constexpr (kStamps) {
+            const unsigned long long now = phase_stamp();
+            st_cull += now - st_prev;
+            st_prev = now;
+            ++rounds;
+        }
+#endif
         if (nh == 0) continue;
         if constexpr (!CLEAR) {
             // in-place: the tile is touched -> fetch its current content into the accumulators NOW, so the load
@@ -381,6 +422,13 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#ifdef ACCV_SPLAT_STAMPS
+        if constexpr (kStamps) {
+            const unsigned long long now = phase_stamp();
+            st_table += now - st_prev;
+            st_prev = now;
+        }
+#endif
 
         // ---- accumulate: per hit PX column factors in registers, row factors from LDS.  Hits are taken two at a time:
         // acc = max3(acc, ex_a * ey_a, ex_b * ey_b) is 3 VALU ops per pixel for two hits instead of 4
@@ -394,13 +442,42 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
                 ex[c] = (colr0 + c >= xlo && colr0 + c < xhi) ? e : __builtin_nanf("");
             }
         };
+        // Both half-waves hold the same columns (different rows), so each half evaluates two of the four factors and the
+        // halves exchange them: v_permlane32_swap of a register with a copy of itself leaves the lower half's value in every
+        // lane of one result and the upper half's in the other.  Same argument and same mask per column: the same factor.
+        // A one-round launch ends with the SIMD whose four waves have the most arithmetic between them (phase stamps,
+        // DESIGN §3), so what counts is instructions per hit: 2 exp + 2 masks + 2 swaps instead of 4 exp + 4 masks
+        [[maybe_unused]] auto column_factors_shared = [&](const Hit& hx, float (&ex)[PX]) {
+            if constexpr (PX == 4) {
+                const unsigned xlo = hx.box & 255u, xhi = (hx.box >> 8) & 255u;
+                unsigned f[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int c = 2 * sub + j;
+                    const float d = (float)(col0 + c - hx.x);
+                    const float e = raw_exp2(-(d * d) * hx.c2);
+                    f[j] = __float_as_uint((colr0 + c >= xlo && colr0 + c < xhi) ? e : __builtin_nanf(""));
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const auto sw = __builtin_amdgcn_permlane32_swap(f[j], f[j], false, false);
+                    ex[j] = __uint_as_float(sw[0]);       // from lanes 0-31: column j
+                    ex[2 + j] = __uint_as_float(sw[1]);   // from lanes 32-63: column 2 + j
+                }
+            }
+        };
         int h = 0;
         // (fused-clear instantiations only: the in-place ones are register bound, and the second set of factors costs
         // them a wave of occupancy — sparse in-place launches lost 5 %)
         for (; CLEAR && h + 1 < nh; h += 2) {
             float exa[PX], exb[PX];
-            column_factors(s_hit[wave][h], exa);
-            column_factors(s_hit[wave][h + 1], exb);
+            if constexpr (kSharedColumns) {
+                column_factors_shared(s_hit[wave][h], exa);
+                column_factors_shared(s_hit[wave][h + 1], exb);
+            } else {
+                column_factors(s_hit[wave][h], exa);
+                column_factors(s_hit[wave][h + 1], exb);
+            }
 #pragma unroll
             for (int q = 0; q < R / 4; ++q) {
                 const float4 a4 = *reinterpret_cast<const float4*>(&s_ey[wave][h][sub * R + 4 * q]);
@@ -415,7 +492,10 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
         }
         for (; h < nh; ++h) {
             float ex[PX];
-            column_factors(s_hit[wave][h], ex);
+            if constexpr (kSharedColumns)
+                column_factors_shared(s_hit[wave][h], ex);
+            else
+                column_factors(s_hit[wave][h], ex);
 #pragma unroll
             for (int q = 0; q < R / 4; ++q) {
                 const float4 e4 = *reinterpret_cast<const float4*>(&s_ey[wave][h][sub * R + 4 * q]);
@@ -427,6 +507,13 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
             }
         }
         total_hits += nh;
+#ifdef ACCV_SPLAT_STAMPS
+        if constexpr (kStamps) {
+            const unsigned long long now = phase_stamp();
+            st_acc += now - st_prev;
+            st_prev = now;
+        }
+#endif
         // the next round overwrites the LDS lists: order it behind this round's reads
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -470,6 +557,23 @@ __device__ __forceinline__ void splat_body(const SplatParams& p, long long linea
             *dst = out;
         }
     }
+#ifdef ACCV_SPLAT_STAMPS
+    if constexpr (kStamps) {
+        const unsigned long long done = phase_stamp();
+        const long long rec = (plane * p.tiles_y + ty0 / TH) * p.tiles_x + tx0 / TW;
+        if (lane == 0 && p.stamps && rec < p.stamp_records) {   // lane 0 owns column tx0 < W and row ty0 < H: never left early
+            unsigned long long* o = p.stamps + 8 * rec;
+            o[0] = st_start;
+            o[1] = st_cull;
+            o[2] = st_table;
+            o[3] = st_acc;
+            o[4] = st_prev;
+            o[5] = (unsigned long long)n;
+            o[6] = done;
+            o[7] = (unsigned long long)(unsigned)total_hits | ((unsigned long long)rounds << 16) | ((unsigned long long)xcc_id() << 32);
+        }
+    }
+#endif
 }
 
 template <int PX, int R, bool CLEAR, int SM, int WPG = kWavesPerGroup>
@@ -1601,6 +1705,11 @@ __global__ void fill_tail_kernel(float* __restrict__ dst, size_t n, float value)
     if (i < n) dst[i] = value;
 }
 
+#ifdef ACCV_SPLAT_STAMPS
+unsigned long long* g_splat_stamps = nullptr;   // diagnostic build: side buffer of the phase stamps (device memory)
+long long g_splat_stamp_records = 0;
+#endif
+
 // store mode sm: 0 plain, 4 write-through non-temporal (sc1 nt), 5 density-adaptive (in-place launches only: a fused-clear
 // launch asking for it gets plain stores).  PX == 1 has plain stores only.
 template <int PX, int R>
@@ -1620,6 +1729,10 @@ int launch_splat(SplatParams p, long long planes, bool clear, int sm, hipStream_
         if (groups > INT_MAX) return accv::fail(ACCV_EINVAL, "draw_heatmap: %lld tiles exceed the grid limit", p.n_tiles);
         grid = dim3((unsigned)groups);
     }
+#ifdef ACCV_SPLAT_STAMPS
+    p.stamps = g_splat_stamps;
+    p.stamp_records = g_splat_stamp_records;
+#endif
     if (PX == 1 || (sm == 5 && clear)) sm = 0;
     if (sm == 5) {
         if constexpr (PX == 4) launch_maybe_timed(splat_kernel<PX, R, false, 5>, grid, block, stream, ev, p);
@@ -2223,3 +2336,13 @@ int accv_fill_f32(float* dst, size_t count, float value, void* stream_)
     return accv::check_launch("fill");
 }
 }
+
+#ifdef ACCV_SPLAT_STAMPS
+// diagnostic build only: fused-clear tile waves of the following splat_kernel launches write 8 x u64 per tile into `buffer`
+// (device memory holding `records` records; nullptr switches the records off)
+extern "C" void accv_debug_splat_stamps(void* buffer, long long records)
+{
+    g_splat_stamps = static_cast<unsigned long long*>(buffer);
+    g_splat_stamp_records = buffer ? records : 0;
+}
+#endif

@@ -72,20 +72,33 @@ def main():
             print(json.dumps({"frames_per_launch": frames, **row}), flush=True)
         return
     if alts:
+        # `--reps N`: N interleaved repetitions (rep -> shard size -> library), so that drift of the box hits every library alike.
+        # Per library and shard size: the slowest shard's time of each repetition, its median and its spread (max - min)
+        reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 1
         libs = {"shipped": lib, **alts}
+        slowest = {(frames, name): [] for frames in (8, 16, 32, 64) for name in libs}
+        fastest = {key: [] for key in slowest}
+        for _ in range(reps):
+            for frames in (8, 16, 32, 64):
+                for name, handle in libs.items():
+                    def one(lo=0, hi=frames, handle=handle):
+                        nat.check(handle.accv_draw_heatmap_batched_f32(hm.data_ptr() + lo * H * W * 4, hi - lo, 0, H, W, c.data_ptr() + lo * nmax * 8,
+                                                                       r.data_ptr() + lo * nmax * 4, n.data_ptr() + lo * 8, None, nmax, 6.0, 1.0,
+                                                                       flags, stream), "draw")
+                    # every shard of the split, slowest one reported (as bench.py's strong-scaling prediction does)
+                    per = []
+                    for k in range(B // frames):
+                        per.append(timed(lambda: one(k * frames, (k + 1) * frames), warm=100, iters=200))
+                    slowest[(frames, name)].append(round(max(per) * 1e3, 2))
+                    fastest[(frames, name)].append(round(min(per) * 1e3, 2))
         for frames in (8, 16, 32, 64):
             row = {}
-            for name, handle in libs.items():
-                def one(lo=0, hi=frames, handle=handle):
-                    nat.check(handle.accv_draw_heatmap_batched_f32(hm.data_ptr() + lo * H * W * 4, hi - lo, 0, H, W, c.data_ptr() + lo * nmax * 8,
-                                                                   r.data_ptr() + lo * nmax * 4, n.data_ptr() + lo * 8, None, nmax, 6.0, 1.0,
-                                                                   flags, stream), "draw")
-                # every shard of the split, slowest one reported (as bench.py's strong-scaling prediction does)
-                per = []
-                for k in range(B // frames):
-                    per.append(timed(lambda: one(k * frames, (k + 1) * frames), warm=100, iters=200))
-                row[name] = {"slowest_us": round(max(per) * 1e3, 2), "fastest_us": round(min(per) * 1e3, 2)}
-            print(json.dumps({"frames_per_launch": frames, **row}))
+            for name in libs:
+                s, f = slowest[(frames, name)], fastest[(frames, name)]
+                row[name] = {"slowest_us": sorted(s)[len(s) // 2], "fastest_us": sorted(f)[len(f) // 2]}
+                if reps > 1:
+                    row[name].update({"slowest_us_all": s, "slowest_us_spread": round(max(s) - min(s), 2), "fastest_us_all": f})
+            print(json.dumps({"frames_per_launch": frames, **row}), flush=True)
         return
     variants = {
         "1 x 64 frames": lambda: split(1),
