@@ -1,5 +1,5 @@
 // Floating-point steps of the f32 polyline sampler that a second kernel has to reproduce BIT FOR BIT: the fused lane raster
-// (draw_heatmap.hip, lane_body) evaluates the samples of a polyline inside the tile wave instead of reading what
+// (splat_lanes.h, lane_body) evaluates the samples of a polyline inside the tile wave instead of reading what
 // polyline_kernel wrote, and both must land on the same pixels.  hipcc contracts a * b + c into an fma where it likes
 // (-ffp-contract=fast is the HIP default), so the few expressions whose rounding matters are spelled out here once —
 // explicit fma where the sampler has always used one, contraction switched off where it has not (checked against the ISA
