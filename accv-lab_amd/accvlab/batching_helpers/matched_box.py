@@ -29,19 +29,22 @@ _FORMATS = {"xyxy": 0, "cxcywh": _nat.MB_CXCYWH}
 
 
 class _Call:
-    """what the forward and the backward C-ABI calls of one invocation share"""
+    """the geometry and scalar parameters that the forward and the backward C-ABI calls of one invocation share; it holds
+    no tensor a kernel reads (avg_dev is read by the forward alone)"""
 
-    def __init__(self, boxes, gt, pind, gind, counts, flags, params, keep):
-        self.gt, self.pind, self.gind, self.counts = gt, pind, gind, counts
-        self.params, self.keep = params, keep   # keep: the tensors the parameter struct points into
+    def __init__(self, boxes, gt, pind, flags, params, avg_dev):
+        self.params, self.avg_dev = params, avg_dev
         self.dev = boxes.device
         self.B, self.Q, self.D = (int(v) for v in boxes.shape)
         self.G, self.K = int(gt.shape[1]), int(pind.shape[1])
         self.flags = flags
         self.out_dtype = torch.float64 if boxes.dtype == torch.float64 else torch.float32
 
-    def inputs(self, boxes):
-        return (boxes.data_ptr(), self.gt.data_ptr(), self.pind.data_ptr(), self.gind.data_ptr(), self.counts.data_ptr())
+    def inputs(self, boxes, gt, pind, gind, counts, weights, cw_dev):
+        """the pointer arguments; the optional operands go into the parameter struct"""
+        self.params.query_weights = None if weights is None else weights.data_ptr()
+        self.params.code_weights_dev = None if cw_dev is None else cw_dev.data_ptr()
+        return (boxes.data_ptr(), gt.data_ptr(), pind.data_ptr(), gind.data_ptr(), counts.data_ptr())
 
     def shape(self, boxes):
         # a dimension of extent 1 may carry any stride
@@ -55,8 +58,9 @@ class _MatchedBoxLoss(torch.autograd.Function):
     """-> (L1 sums [B], IoU sums [B]), the two rows of one [2, B] tensor"""
 
     @staticmethod
-    def forward(ctx, call, boxes):
+    def forward(ctx, call, boxes, gt, pind, gind, counts, weights, cw_dev):
         dev = call.dev
+        tensors = (boxes, gt, pind, gind, counts, weights, cw_dev)
         run = call.B * call.Q * call.K > 0
         out = (torch.empty if run else torch.zeros)((2, call.B), dtype=call.out_dtype, device=dev)
         denom = torch.empty((), dtype=torch.float64, device=dev)
@@ -66,13 +70,14 @@ class _MatchedBoxLoss(torch.autograd.Function):
                 nbytes = lib.accv_matched_box_loss_workspace_bytes(call.B, call.Q, call.D)
                 ws = _nat.workspace(nbytes, dev)
                 with _nat.device_guard(dev):
-                    _nat.check(lib.accv_matched_box_loss(*call.inputs(boxes), *call.shape(boxes), out.data_ptr(),
+                    _nat.check(lib.accv_matched_box_loss(*call.inputs(*tensors), *call.shape(boxes), out.data_ptr(),
                                                          denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
             else:
-                _nat.check(lib.accv_matched_box_loss_host(*call.inputs(boxes), *call.shape(boxes), out.data_ptr(),
+                _nat.check(lib.accv_matched_box_loss_host(*call.inputs(*tensors), *call.shape(boxes), out.data_ptr(),
                                                           denom.data_ptr()), _WHO)
         ctx.call, ctx.run = call, run
-        ctx.save_for_backward(boxes, denom)
+        # everything the backward kernel reads: alive until then, and guarded by torch's version check
+        ctx.save_for_backward(denom, *tensors)
         ctx.set_materialize_grads(False)   # an unused output arrives as None and goes down as a null pointer
         return out[0], out[1]
 
@@ -80,23 +85,24 @@ class _MatchedBoxLoss(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_l1, grad_iou):
         call = ctx.call
-        boxes, denom = ctx.saved_tensors
+        denom, *tensors = ctx.saved_tensors
+        boxes = tensors[0]
         if not ctx.needs_input_grad[1]:
-            return None, None
+            return (None,) * 8
         if not ctx.run:   # no pair anywhere: nothing depends on the boxes
-            return None, torch.zeros(boxes.shape, dtype=boxes.dtype, device=call.dev)
+            return (None, torch.zeros(boxes.shape, dtype=boxes.dtype, device=call.dev)) + (None,) * 6
         grad = torch.empty(boxes.shape, dtype=boxes.dtype, device=call.dev)   # contiguous, written completely
         grad_l1 = None if grad_l1 is None else grad_l1.to(call.out_dtype).contiguous()
         grad_iou = None if grad_iou is None else grad_iou.to(call.out_dtype).contiguous()
         lib = _nat.lib()
-        args = (*call.inputs(boxes), None if grad_l1 is None else grad_l1.data_ptr(),
+        args = (*call.inputs(*tensors), None if grad_l1 is None else grad_l1.data_ptr(),   # re-points the struct
                 None if grad_iou is None else grad_iou.data_ptr(), denom.data_ptr(), *call.shape(boxes), grad.data_ptr())
         if call.dev.type == "cuda":
             with _nat.device_guard(call.dev):
                 _nat.check(lib.accv_matched_box_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
         else:
             _nat.check(lib.accv_matched_box_loss_bwd_host(*args), _WHO + " backward")
-        return None, grad
+        return (None, grad) + (None,) * 6
 
 
 def _ragged(name, rb, what, dims):
@@ -161,7 +167,9 @@ def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: 
     are never read.  A frame without pairs gives 0.  ``B``, ``Q`` or ``K`` of 0 give zeros and launch nothing.
 
     Returns two ``[B]`` tensors, float32 (float64 for float64 boxes).  Differentiable w.r.t. ``pred_boxes`` only, for
-    either or both outputs (no double backward); the gradient has the boxes' dtype, is contiguous and written completely,
+    either or both outputs (no double backward).  The tensors read by the backward (both box tensors, both index tensors,
+    ``pred_ind.sample_sizes``, ``query_weights``, a tensor ``code_weights``) are saved; modifying them in place before
+    ``backward()`` raises.  The gradient has the boxes' dtype, is contiguous and written completely,
     ``+0`` for unmatched queries.  It is the closed-form chain rule with float64 autograd's conventions where the
     definition is not smooth: an exact tie of a maximum / minimum splits the gradient evenly, a floor that fires passes
     none, ``|0|`` has gradient 0.  float16 / bfloat16 boxes are widened exactly and evaluated in float32, float64 in
@@ -254,8 +262,6 @@ def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: 
     for d in range(D):
         params.code_weights[d] = 1.0 if cw_values is None else cw_values[d]
     params.avg_factor_dev = None if avg_dev is None else avg_dev.data_ptr()
-    params.code_weights_dev = None if cw_dev is None else cw_dev.data_ptr()
-    params.query_weights = None if weights is None else weights.data_ptr()
     flags = (_nat.MB_IDX_I64 if pind.dtype == torch.int64 else 0) | _FORMATS[box_format]
-    call = _Call(pred_boxes, gt, pind, gind, counts, flags, params, (avg_dev, cw_dev, weights))
-    return _MatchedBoxLoss.apply(call, pred_boxes)
+    call = _Call(pred_boxes, gt, pind, flags, params, avg_dev)
+    return _MatchedBoxLoss.apply(call, pred_boxes, gt, pind, gind, counts, weights, cw_dev)

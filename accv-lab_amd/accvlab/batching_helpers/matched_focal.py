@@ -40,10 +40,10 @@ def _params(alpha, gamma, mode, value, avg_dev):
 
 
 class _Call:
-    """what the forward and the backward C-ABI calls of one invocation share"""
+    """the geometry and scalar parameters that the forward and the backward C-ABI calls of one invocation share; it holds
+    no tensor a kernel reads (avg_dev is read by the forward alone)"""
 
-    def __init__(self, logits, labels, pind, gind, counts, weights, params, avg_dev):
-        self.labels, self.pind, self.gind, self.counts, self.weights = labels, pind, gind, counts, weights
+    def __init__(self, logits, labels, pind, params, avg_dev):
         self.params, self.avg_dev = params, avg_dev
         self.dev = logits.device
         self.B, self.Q, self.C = (int(v) for v in logits.shape)
@@ -52,9 +52,10 @@ class _Call:
                      (_nat.MF_LABELS_I64 if labels.dtype == torch.int64 else 0)
         self.out_dtype = torch.float64 if logits.dtype == torch.float64 else torch.float32
 
-    def inputs(self, logits):
-        return (logits.data_ptr(), self.labels.data_ptr(), self.pind.data_ptr(), self.gind.data_ptr(),
-                self.counts.data_ptr(), None if self.weights is None else self.weights.data_ptr())
+    @staticmethod
+    def inputs(logits, labels, pind, gind, counts, weights):
+        return (logits.data_ptr(), labels.data_ptr(), pind.data_ptr(), gind.data_ptr(), counts.data_ptr(),
+                None if weights is None else weights.data_ptr())
 
     def shape(self, logits):
         # a dimension of extent 1 may carry any stride
@@ -66,8 +67,9 @@ class _Call:
 
 class _MatchedFocalLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, call, logits):
+    def forward(ctx, call, logits, labels, pind, gind, counts, weights):
         dev = call.dev
+        tensors = (logits, labels, pind, gind, counts, weights)
         n = call.B * call.Q * call.C
         out = (torch.empty if n > 0 else torch.zeros)((call.B,), dtype=call.out_dtype, device=dev)
         denom = torch.empty((), dtype=torch.float64, device=dev)
@@ -77,33 +79,35 @@ class _MatchedFocalLoss(torch.autograd.Function):
                 nbytes = lib.accv_matched_focal_loss_workspace_bytes(call.B, call.Q, call.C)
                 ws = _nat.workspace(nbytes, dev)
                 with _nat.device_guard(dev):
-                    _nat.check(lib.accv_matched_focal_loss(*call.inputs(logits), *call.shape(logits), out.data_ptr(),
+                    _nat.check(lib.accv_matched_focal_loss(*call.inputs(*tensors), *call.shape(logits), out.data_ptr(),
                                                            denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
             else:
-                _nat.check(lib.accv_matched_focal_loss_host(*call.inputs(logits), *call.shape(logits), out.data_ptr(),
+                _nat.check(lib.accv_matched_focal_loss_host(*call.inputs(*tensors), *call.shape(logits), out.data_ptr(),
                                                             denom.data_ptr()), _WHO)
         ctx.call = call
-        ctx.save_for_backward(logits, denom)
+        # everything the backward kernel reads: alive until then, and guarded by torch's version check
+        ctx.save_for_backward(denom, *tensors)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         call = ctx.call
-        logits, denom = ctx.saved_tensors
+        denom, *tensors = ctx.saved_tensors
+        logits = tensors[0]
         if not ctx.needs_input_grad[1]:
-            return None, None
+            return (None,) * 7
         grad = torch.empty(logits.shape, dtype=logits.dtype, device=call.dev)   # contiguous, written completely
         if grad.numel() > 0:
             grad_out = grad_out.to(call.out_dtype).contiguous()
             lib = _nat.lib()
-            args = (*call.inputs(logits), grad_out.data_ptr(), denom.data_ptr(), *call.shape(logits), grad.data_ptr())
+            args = (*call.inputs(*tensors), grad_out.data_ptr(), denom.data_ptr(), *call.shape(logits), grad.data_ptr())
             if call.dev.type == "cuda":
                 with _nat.device_guard(call.dev):
                     _nat.check(lib.accv_matched_focal_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
             else:
                 _nat.check(lib.accv_matched_focal_loss_bwd_host(*args), _WHO + " backward")
-        return None, grad
+        return None, grad, None, None, None, None, None
 
 
 def _ragged(name, rb, what):
@@ -162,6 +166,8 @@ def matched_focal_loss(pred_logits: torch.Tensor, gt_labels: RaggedBatch, pred_i
 
     Returns ``[B]`` float32 (float64 for float64 logits), so that it adds to what ``matched_pair_loss_sum`` returns.
     Differentiable w.r.t. ``pred_logits`` only (no double backward); the gradient has the logits' dtype and is contiguous.
+    The tensors read by the backward (logits, labels, both index tensors, ``pred_ind.sample_sizes``, ``query_weights``) are
+    saved; modifying them in place before ``backward()`` raises.
     float16 / bfloat16 logits are widened exactly and evaluated in float32, float64 in float64; ``s``, ``1 - s`` and both
     softplus values come from ``exp(-|x|)`` without cancellation; sums are accumulated in float64 in a fixed order, so
     forward and backward are bitwise reproducible.  Two launches forward, one backward (every gradient element written
@@ -223,5 +229,5 @@ def matched_focal_loss(pred_logits: torch.Tensor, gt_labels: RaggedBatch, pred_i
 
     mode, value, avg_dev = _nat.avg_factor_args(avg_factor, dev, _WHO, ValueError, "the logits' device")
     counts = sizes.detach().to(torch.int64).contiguous()
-    call = _Call(pred_logits, labels, pind, gind, counts, weights, _params(alpha, gamma, mode, value, avg_dev), avg_dev)
-    return _MatchedFocalLoss.apply(call, pred_logits)
+    call = _Call(pred_logits, labels, pind, _params(alpha, gamma, mode, value, avg_dev), avg_dev)
+    return _MatchedFocalLoss.apply(call, pred_logits, labels, pind, gind, counts, weights)

@@ -10,7 +10,9 @@ from . import batched_indexing_access_cuda as _gpu
 class SetPaddedTo(torch.autograd.Function):
     """``data[i, j, ...] = value`` for ``j >= sample_sizes[i]``.  Operates in place on ``data`` when it is
     contiguous (otherwise on a contiguous copy) and returns the filled tensor.  Backward: the incoming
-    gradient with its padding zeroed."""
+    gradient with its padding zeroed, as an output of this Function, so that a second derivative sees the
+    same mask.  ``sample_sizes`` is read by the backward and saved; modifying it in place before
+    ``backward()`` raises."""
 
     @staticmethod
     def forward(ctx, data: torch.Tensor, sample_sizes: torch.Tensor, value_to_set):
@@ -27,6 +29,4 @@ class SetPaddedTo(torch.autograd.Function):
     def backward(ctx, grad_output):
         if grad_output is None:
             return None, None, None
-        grad = grad_output.clone()
-        SetPaddedTo.apply(grad, ctx.saved_tensors[0], 0.0)
-        return grad, None, None
+        return SetPaddedTo.apply(grad_output.clone(), ctx.saved_tensors[0], 0.0), None, None

@@ -91,7 +91,8 @@ def _check_ragged_centers(who, centers, first):
 
 
 class _Call:
-    """what every C-ABI call of one operator invocation shares: the host arrays of the maps and the centres"""
+    """the geometry that every C-ABI call of one operator invocation shares: the host array of the channel counts, the
+    shapes of the maps and of the centres; it holds no tensor a kernel reads"""
 
     def __init__(self, maps, where, sizes, index_form):
         self.n = len(maps)
@@ -100,51 +101,61 @@ class _Call:
         self.B, _, self.H, self.W = maps[0].shape
         self.channels = (ctypes.c_int * self.n)(*[m.shape[1] for m in maps])
         self.C = sum(self.channels)
-        self.where, self.sizes = where, sizes
+        self.map_dtype = maps[0].dtype
+        self.shapes = [tuple(m.shape) for m in maps]
         self.N = where.shape[1]
         self.flags = _nat.CR_INDEX_FORM if index_form else (_nat.CR_COUNTS_I64 if sizes.dtype == torch.int64 else 0)
 
     def pointers(self, tensors):
         return (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in tensors])
 
-    def geometry(self):
-        return (ctypes.addressof(self.channels), self.n, self.dtype, self.B, self.H, self.W, self.where.data_ptr(),
-                None if self.sizes is None else self.sizes.data_ptr(), self.N)
+    def geometry(self, where, sizes):
+        return (ctypes.addressof(self.channels), self.n, self.dtype, self.B, self.H, self.W, where.data_ptr(),
+                None if sizes is None else sizes.data_ptr(), self.N)
+
+    def empty_maps(self, needed):
+        """uninitialised gradient maps (contiguous, as the maps are) where `needed`, None elsewhere"""
+        return [torch.empty(shape, dtype=self.map_dtype, device=self.dev) if need else None
+                for shape, need in zip(self.shapes, needed)]
 
 
 class _GatherAtCenters(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, call, *maps):
+    def forward(ctx, call, where, sizes, *maps):
         out = torch.empty((call.B, call.N, call.C), dtype=maps[0].dtype, device=call.dev)
         if out.numel() > 0:
             ptrs = call.pointers(maps)
             with _nat.device_guard(call.dev):
-                _nat.check(_nat.lib().accv_gather_at_centers(ctypes.addressof(ptrs), *call.geometry(), call.flags,
-                                                             out.data_ptr(), _nat.stream_ptr(call.dev)), "gather_at_centers")
+                _nat.check(_nat.lib().accv_gather_at_centers(ctypes.addressof(ptrs), *call.geometry(where, sizes),
+                                                             call.flags, out.data_ptr(), _nat.stream_ptr(call.dev)),
+                           "gather_at_centers")
         ctx.call = call
-        ctx.save_for_backward(*maps)
+        # the scatter reads the centres and the sample sizes, never the maps: those are neither kept alive nor guarded
+        ctx.save_for_backward(where, sizes)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
-        call, maps = ctx.call, ctx.saved_tensors
-        grads = [torch.empty_like(m) if need else None for m, need in zip(maps, ctx.needs_input_grad[1:])]
+        call = ctx.call
+        where, sizes = ctx.saved_tensors
+        grads = call.empty_maps(ctx.needs_input_grad[3:])
         if any(g is not None and g.numel() > 0 for g in grads):
             # the kernel writes every map of the call; one that needs no gradient still gets a buffer
-            bufs = [torch.empty_like(m) if g is None else g for m, g in zip(maps, grads)]
+            spare = call.empty_maps([g is None for g in grads])
+            bufs = [s if g is None else g for s, g in zip(spare, grads)]
             grad = grad.contiguous()
             ptrs = call.pointers(bufs)
             with _nat.device_guard(call.dev):
-                _nat.check(_nat.lib().accv_scatter_at_centers(ctypes.addressof(ptrs), *call.geometry(), call.flags,
-                                                              grad.data_ptr(), _nat.stream_ptr(call.dev)),
+                _nat.check(_nat.lib().accv_scatter_at_centers(ctypes.addressof(ptrs), *call.geometry(where, sizes),
+                                                              call.flags, grad.data_ptr(), _nat.stream_ptr(call.dev)),
                            "gather_at_centers backward")
-        return (None, *grads)
+        return (None, None, None, *grads)
 
 
 class _CenterRegressionLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, call, targets, weights, params, avg_factor, *maps):
+    def forward(ctx, call, where, sizes, targets, weights, params, avg_factor, *maps):
         dev = call.dev
         loss = torch.zeros((), dtype=torch.float32, device=dev) if call.B == 0 else torch.empty((), dtype=torch.float32, device=dev)
         denom = torch.empty((), dtype=torch.float32, device=dev)
@@ -155,32 +166,33 @@ class _CenterRegressionLoss(torch.autograd.Function):
             ptrs = call.pointers(maps)
             with _nat.device_guard(dev):
                 _nat.check(lib.accv_center_regression_loss(
-                    ctypes.addressof(ptrs), *call.geometry(), flags, targets.data_ptr(),
+                    ctypes.addressof(ptrs), *call.geometry(where, sizes), flags, targets.data_ptr(),
                     None if weights is None else weights.data_ptr(), ctypes.addressof(params),
                     avg_factor.data_ptr() if isinstance(avg_factor, torch.Tensor) else None, loss.data_ptr(),
                     denom.data_ptr(), ws.data_ptr(), ws.numel(), _nat.stream_ptr(dev)), "center_regression_loss")
         ctx.call, ctx.flags, ctx.params = call, flags, params
         ctx.has_weights = weights is not None
-        ctx.save_for_backward(targets, denom, *(() if weights is None else (weights,)), *maps)
+        # everything the backward kernel reads: alive until then, and guarded by torch's version check
+        ctx.save_for_backward(where, sizes, targets, denom, *(() if weights is None else (weights,)), *maps)
         return loss
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
         call = ctx.call
-        targets, denom, *rest = ctx.saved_tensors
+        where, sizes, targets, denom, *rest = ctx.saved_tensors
         weights, maps = (rest[0], rest[1:]) if ctx.has_weights else (None, rest)
-        grads = [torch.empty_like(m) if need else None for m, need in zip(maps, ctx.needs_input_grad[5:])]
+        grads = [torch.empty_like(m) if need else None for m, need in zip(maps, ctx.needs_input_grad[7:])]
         if any(g is not None and g.numel() > 0 for g in grads):
             bufs = [torch.empty_like(m) if g is None else g for m, g in zip(maps, grads)]
             grad = grad.contiguous().to(torch.float32)
             feat_ptrs, grad_ptrs = call.pointers(maps), call.pointers(bufs)
             with _nat.device_guard(call.dev):
                 _nat.check(_nat.lib().accv_center_regression_loss_bwd(
-                    ctypes.addressof(feat_ptrs), ctypes.addressof(grad_ptrs), *call.geometry(), ctx.flags,
+                    ctypes.addressof(feat_ptrs), ctypes.addressof(grad_ptrs), *call.geometry(where, sizes), ctx.flags,
                     targets.data_ptr(), None if weights is None else weights.data_ptr(), ctypes.addressof(ctx.params),
                     grad.data_ptr(), denom.data_ptr(), _nat.stream_ptr(call.dev)), "center_regression_loss backward")
-        return (None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, *grads)
 
 
 def gather_at_centers(feats: Union[torch.Tensor, Sequence[torch.Tensor]], where):
@@ -201,7 +213,9 @@ def gather_at_centers(feats: Union[torch.Tensor, Sequence[torch.Tensor]], where)
     bit-exact copies of ``feats[i][b, :, y, x]``, every other row (padding, centres outside the map) is exactly 0, and
     nothing outside the maps is ever read.
 
-    Differentiable w.r.t. every tensor in ``feats`` (gradient in their dtype; no double backward).  The backward is one
+    Differentiable w.r.t. every tensor in ``feats`` (gradient in their dtype; no double backward).  The tensors read by
+    the backward (the centres and their sample sizes, or the indices) are saved; modifying them in place before
+    ``backward()`` raises.  The maps are not read again: they are not kept alive and may change.  The backward is one
     kernel that writes the gradient maps completely — zeros, and at each valid cell the sum of the rows that name it, in
     ascending slot order, accumulated in float32 and rounded once — without atomics, so it is bitwise reproducible.  One
     launch per direction on torch's current stream; no host synchronisation.
@@ -218,8 +232,8 @@ def gather_at_centers(feats: Union[torch.Tensor, Sequence[torch.Tensor]], where)
     maps = _check_feats(who, feats)
     first = maps[0]
     if _is_ragged(where):
-        c_t, sizes = _check_ragged_centers(who, where, first)
-        call = _Call(maps, c_t, sizes, False)
+        call_where, call_sizes = _check_ragged_centers(who, where, first)
+        call = _Call(maps, call_where, call_sizes, False)
     else:
         if not isinstance(where, torch.Tensor):
             raise RuntimeError(f"{who}: where must be a RaggedBatch of int32 centres or an int64 tensor [B, K] of indices")
@@ -230,8 +244,9 @@ def gather_at_centers(feats: Union[torch.Tensor, Sequence[torch.Tensor]], where)
                                f"{tuple(where.shape)}")
         if not where.is_contiguous():
             raise RuntimeError(f"{who}: indices must be contiguous")
+        call_where, call_sizes = where, None
         call = _Call(maps, where, None, True)
-    out = _GatherAtCenters.apply(call, *maps)
+    out = _GatherAtCenters.apply(call, call_where, call_sizes, *maps)
     from ..batching_helpers import RaggedBatch
 
     return RaggedBatch(out, sample_sizes=where.sample_sizes) if _is_ragged(where) else out
@@ -259,7 +274,9 @@ def center_regression_loss(feats: Union[torch.Tensor, Sequence[torch.Tensor]], c
     fixed order, so the same inputs give the same bits on every run.  Differentiable w.r.t. every tensor in ``feats``
     (gradient in their dtype; no double backward) through the complete-write kernel of :func:`gather_at_centers`'s
     backward: the contribution of a slot is ``(w * l'(d)) * (grad / denom)`` in float32, several objects on one cell add
-    up in ascending slot order.  Two launches forward, one backward, on torch's current stream; no host synchronisation.
+    up in ascending slot order.  The tensors read by the backward (maps, centres, sample sizes, targets, weights) are
+    saved; modifying them in place before ``backward()`` raises.  Two launches forward, one backward, on torch's current
+    stream; no host synchronisation.
 
     Special values follow float64 autograd of the definition: NaN / inf in a read cell, target or weight reach the loss
     and that cell's gradient; whatever invalid slots, unread cells or unread target rows hold reaches nothing.
@@ -294,4 +311,4 @@ def center_regression_loss(feats: Union[torch.Tensor, Sequence[torch.Tensor]], c
     mode, value, avg_factor = _nat.avg_factor_args(avg_factor, first.device, who, RuntimeError, "the maps' device")
     params = _nat.CenterRegressionParams(_KINDS[kind], mode, float(beta), value)
     call = _Call(maps, c_t, sizes, False)
-    return _CenterRegressionLoss.apply(call, targets, weights, params, avg_factor, *maps)
+    return _CenterRegressionLoss.apply(call, c_t, sizes, targets, weights, params, avg_factor, *maps)

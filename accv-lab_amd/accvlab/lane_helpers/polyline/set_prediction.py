@@ -214,19 +214,21 @@ _WHO = "matched_polyline_loss"
 
 
 class _Call:
-    """what the forward and the backward C-ABI calls of one invocation share"""
+    """the geometry and scalar parameters that the forward and the backward C-ABI calls of one invocation share; it holds
+    no tensor a kernel reads (avg_dev is read by the forward alone)"""
 
-    def __init__(self, lines, gt, pind, gind, counts, flags, params, keep, dims):
-        self.gt, self.pind, self.gind, self.counts = gt, pind, gind, counts
-        self.params, self.keep = params, keep   # keep: the tensors the parameter struct points into
+    def __init__(self, lines, pind, flags, params, avg_dev, dims):
+        self.params, self.avg_dev = params, avg_dev
         self.dev = lines.device
         self.B, self.Q, self.G, self.P, self.D = dims
         self.K = int(pind.shape[1])
         self.flags = flags
         self.out_dtype = torch.float64 if lines.dtype == torch.float64 else torch.float32
 
-    def inputs(self, lines):
-        return (lines.data_ptr(), self.gt.data_ptr(), self.pind.data_ptr(), self.gind.data_ptr(), self.counts.data_ptr())
+    def inputs(self, lines, gt, pind, gind, counts, closed):
+        """the pointer arguments; the optional operand goes into the parameter struct"""
+        self.params.gt_closed = None if closed is None else closed.data_ptr()
+        return (lines.data_ptr(), gt.data_ptr(), pind.data_ptr(), gind.data_ptr(), counts.data_ptr())
 
     def shape(self, lines):
         return (_DTYPES[lines.dtype], self.flags, self.B, self.Q, self.G, self.P, self.D, self.K,
@@ -237,8 +239,9 @@ class _MatchedPolylineLoss(torch.autograd.Function):
     """-> (point sums [B], direction sums [B]), the two rows of one [2, B] tensor"""
 
     @staticmethod
-    def forward(ctx, call, lines):
+    def forward(ctx, call, lines, gt, pind, gind, counts, closed):
         dev = call.dev
+        tensors = (lines, gt, pind, gind, counts, closed)
         run = call.B * call.Q * call.K > 0
         out = (torch.empty if run else torch.zeros)((2, call.B), dtype=call.out_dtype, device=dev)
         denom = torch.empty((), dtype=torch.float64, device=dev)
@@ -248,14 +251,15 @@ class _MatchedPolylineLoss(torch.autograd.Function):
                 nbytes = lib.accv_matched_polyline_loss_workspace_bytes(call.B, call.Q)
                 ws = _nat.workspace(nbytes, dev)
                 with _nat.device_guard(dev):
-                    _nat.check(lib.accv_matched_polyline_loss(*call.inputs(lines), *call.shape(lines), out.data_ptr(),
+                    _nat.check(lib.accv_matched_polyline_loss(*call.inputs(*tensors), *call.shape(lines), out.data_ptr(),
                                                               denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)),
                                _WHO)
             else:
-                _nat.check(lib.accv_matched_polyline_loss_host(*call.inputs(lines), *call.shape(lines), out.data_ptr(),
+                _nat.check(lib.accv_matched_polyline_loss_host(*call.inputs(*tensors), *call.shape(lines), out.data_ptr(),
                                                                denom.data_ptr()), _WHO)
         ctx.call, ctx.run = call, run
-        ctx.save_for_backward(lines, denom)
+        # everything the backward kernel reads: alive until then, and guarded by torch's version check
+        ctx.save_for_backward(denom, *tensors)
         ctx.set_materialize_grads(False)   # an unused output arrives as None and goes down as a null pointer
         return out[0], out[1]
 
@@ -263,23 +267,24 @@ class _MatchedPolylineLoss(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_pts, grad_dir):
         call = ctx.call
-        lines, denom = ctx.saved_tensors
+        denom, *tensors = ctx.saved_tensors
+        lines = tensors[0]
         if not ctx.needs_input_grad[1]:
-            return None, None
+            return (None,) * 7
         if not ctx.run:   # no pair anywhere: nothing depends on the lines
-            return None, torch.zeros(lines.shape, dtype=lines.dtype, device=call.dev)
+            return (None, torch.zeros(lines.shape, dtype=lines.dtype, device=call.dev)) + (None,) * 5
         grad = torch.empty(lines.shape, dtype=lines.dtype, device=call.dev)   # contiguous, written completely
         grad_pts = None if grad_pts is None else grad_pts.to(call.out_dtype).contiguous()
         grad_dir = None if grad_dir is None else grad_dir.to(call.out_dtype).contiguous()
         lib = _nat.lib()
-        args = (*call.inputs(lines), None if grad_pts is None else grad_pts.data_ptr(),
+        args = (*call.inputs(*tensors), None if grad_pts is None else grad_pts.data_ptr(),   # re-points the struct
                 None if grad_dir is None else grad_dir.data_ptr(), denom.data_ptr(), *call.shape(lines), grad.data_ptr())
         if call.dev.type == "cuda":
             with _nat.device_guard(call.dev):
                 _nat.check(lib.accv_matched_polyline_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
         else:
             _nat.check(lib.accv_matched_polyline_loss_bwd_host(*args), _WHO + " backward")
-        return None, grad
+        return (None, grad) + (None,) * 5
 
 
 def _index(name, rb):
@@ -318,8 +323,10 @@ def matched_polyline_loss(pred_lines: torch.Tensor, gt_lines: RaggedBatch, pred_
     A frame without pairs gives 0; ``B``, ``Q`` or ``K`` of 0 give zeros and launch nothing.
 
     Returns two ``[B]`` tensors, float32 (float64 for float64 lines).  Differentiable w.r.t. ``pred_lines`` only, for either
-    or both outputs (no double backward).  ``v*`` is a constant of the backward (what ``torch.min(dim)`` and a gather by
-    order index do) and is searched again there; ``|0|`` has gradient 0.  The gradient has the lines' dtype, is contiguous
+    or both outputs (no double backward).  The tensors read by the backward (both line tensors, both index tensors,
+    ``pred_ind.sample_sizes``, ``gt_closed``) are saved; modifying them in place before ``backward()`` raises.  ``v*`` is a
+    constant of the backward (what ``torch.min(dim)`` and a gather by order index do) and is searched again there; ``|0|``
+    has gradient 0.  The gradient has the lines' dtype, is contiguous
     and written completely, ``+0`` for unmatched queries, without atomics or a zero fill.  Per-frame sums are accumulated in
     float64 in a fixed order: both directions are bitwise reproducible, run on torch's current stream without host
     synchronisation and can be captured into a graph.  Two launches forward, one backward.
@@ -350,7 +357,6 @@ def matched_polyline_loss(pred_lines: torch.Tensor, gt_lines: RaggedBatch, pred_
     params.dir_eps, params.avg_factor, params.avg_mode, params.dir_loss = dir_eps, value, mode, 1 if dir_loss else 0
     params.pred_stride_b, params.pred_stride_q = sb, sq
     params.avg_factor_dev = None if avg_dev is None else avg_dev.data_ptr()
-    params.gt_closed = None if closed is None else closed.data_ptr()
     flags = ((_nat.PM_IDX_I64 if pind.dtype == torch.int64 else 0) | (_nat.PM_REVERSIBLE if reversible else 0) | closed_flag)
-    call = _Call(pred_lines, gt, pind, gind, counts, flags, params, (avg_dev, closed), (B, Q, G, P, D))
-    return _MatchedPolylineLoss.apply(call, pred_lines)
+    call = _Call(pred_lines, pind, flags, params, avg_dev, (B, Q, G, P, D))
+    return _MatchedPolylineLoss.apply(call, pred_lines, gt, pind, gind, counts, closed)
