@@ -2,9 +2,10 @@
 share.
 
 Definition: torchvision's ``sigmoid_focal_loss`` / mmdet's ``py_sigmoid_focal_loss`` on one-hot targets built from the
-matching, evaluated in float64 with autograd on the dtype-rounded inputs.  A pair (slot ``j < clamp(n_b, 0, K)``) NAMES
-its query when both of its indices are in range; the lowest slot that names a query decides its row, also when that
-slot's label is outside ``[0, C)`` (the row then stays all-background).
+matching, evaluated in float64 with autograd on the dtype-rounded inputs, in the cancellation-free form of
+``elementwise_stable`` (the textbook spelling, ``definition_textbook``, loses the gradient's digits for |x| >~ 28).
+A pair (slot ``j < clamp(n_b, 0, K)``) NAMES its query when both of its indices are in range; the lowest slot that names
+a query decides its row, also when that slot's label is outside ``[0, C)`` (the row then stays all-background).
 
 Tolerances: per-frame loss 1e-5 relative to the float64 value (float64: 1e-12); float32 gradients
 ``|g - g64| <= 1e-4 |g64| + 1e-6 max|g64|``; float16 / bfloat16 gradients within one unit in the last place of the float64
@@ -59,6 +60,23 @@ def shape_case(B, Q, C, max_objects, dtype, seed=0, device="cpu", **kw):
     return make_case(B, Q, C, sizes, sizes, dtype, seed=seed, device=device, **kw)
 
 
+TAIL_LOGITS = [33.0, 35.0, 37.0, 40.0, -33.0, -37.0]    # exact in every dtype; 1 - sigmoid loses 1 % .. 100 % in float64 there
+
+
+def deep_tail_case(dtype, sigma, device="cpu", seed=21):
+    """make_case(5, 100, 11) with logits ~ N(0, sigma^2) (sigma 8 or 16: most sigmoids saturated) and, so that the saturated
+    tails are reached on both kinds of element whatever the draw, TAIL_LOGITS planted in frame 1 on its six matched
+    (query, label) elements and on the next class of the same queries (background elements)"""
+    sizes, pairs = [0, 6, 3, 1, 6], [0, 6, 2, 1, 6]
+    inp = make_case(5, 100, 11, sizes, pairs, dtype, seed=seed, weights=True, sigma=sigma, device=device)
+    logits, labels, pind, gind, _ = inp
+    for j, v in enumerate(TAIL_LOGITS):
+        q, c = int(pind.tensor[1, j]), int(labels.tensor[1, int(gind.tensor[1, j])])
+        logits[1, q, c] = v
+        logits[1, q, (c + 1) % 11] = v
+    return inp
+
+
 def targets(logits, gt_labels, pred_ind, gt_ind):
     """the one-hot target [B, Q, C] (float64, on the CPU) of the definition"""
     B, Q, C = logits.shape
@@ -78,16 +96,42 @@ def targets(logits, gt_labels, pred_ind, gt_ind):
     return t
 
 
-def definition(logits, gt_labels, pred_ind, gt_ind, alpha=0.25, gamma=2.0, query_weights=None, avg_factor=None,
-               grad_out=None):
-    """-> (out [B] float64, d sum(out * grad_out) / d logits [B, Q, C] float64, factor), on the CPU"""
-    t = targets(logits, gt_labels, pred_ind, gt_ind)
-    x = logits.detach().cpu().double().clone().requires_grad_(True)
+def elementwise_stable(x, t, alpha, gamma):
+    """the focal term per element without a cancelling subtraction: ``softplus(-x) sigmoid(-x)^gamma`` where t = 1,
+    ``softplus(x) sigmoid(x)^gamma`` where t = 0, with ``softplus(-z) = -logsigmoid(z)`` and
+    ``sigmoid(z)^gamma = exp(gamma logsigmoid(z))``: every factor, and every factor of the autograd gradient, is a
+    product of values that keep their relative precision however far the sigmoid saturates"""
+    ls = torch.nn.functional.logsigmoid
+    z = torch.where(t > 0.5, x, -x)                    # the logit seen from the element's own class
+    loss = -ls(z) * torch.exp(gamma * ls(-z))
+    if alpha >= 0:
+        loss = (alpha * t + (1 - alpha) * (1 - t)) * loss
+    return loss
+
+
+def elementwise_textbook(x, t, alpha, gamma):
+    """torchvision's ``sigmoid_focal_loss`` as written: ``1 - p_t`` cancels once ``1 - p`` is within a few units in the
+    last place of 1 (float64: |x| >~ 28)"""
     p = x.sigmoid()
     ce = torch.nn.functional.binary_cross_entropy_with_logits(x, t, reduction="none")
     loss = ce * (1 - (p * t + (1 - p) * (1 - t))) ** gamma
     if alpha >= 0:
         loss = (alpha * t + (1 - alpha) * (1 - t)) * loss
+    return loss
+
+
+def definition_textbook(*args, **kw):
+    """`definition` with the textbook form of the element term: accurate for |x| <= 20
+    (test_matched_focal_loss_cpu.py::test_stable_and_textbook_definitions_agree_up_to_20), wrong in the deep tails"""
+    return definition(*args, elementwise=elementwise_textbook, **kw)
+
+
+def definition(logits, gt_labels, pred_ind, gt_ind, alpha=0.25, gamma=2.0, query_weights=None, avg_factor=None,
+               grad_out=None, elementwise=elementwise_stable):
+    """-> (out [B] float64, d sum(out * grad_out) / d logits [B, Q, C] float64, factor), on the CPU"""
+    t = targets(logits, gt_labels, pred_ind, gt_ind)
+    x = logits.detach().cpu().double().clone().requires_grad_(True)
+    loss = elementwise(x, t, alpha, gamma)
     if query_weights is not None:
         loss = loss * query_weights.detach().cpu().double()[..., None]
     if avg_factor is None:

@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from matched_focal_loss_cases import (DTYPES, bits, check_grad, check_loss, definition, end_to_end, make_case,  # noqa: E402
-                                      ragged, run, shape_case)
+from matched_focal_loss_cases import (DTYPES, bits, check_grad, check_loss, deep_tail_case, definition, end_to_end,  # noqa: E402
+                                      make_case, ragged, run, shape_case)
 
 from accvlab.batching_helpers import matched_focal_loss as mfl  # noqa: E402
 
@@ -288,3 +288,14 @@ def test_infinite_logits_device_and_host_agree(dtype):
 
 def test_end_to_end_chain_equals_the_composition():
     end_to_end(DEV, ragged_ops=True)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=name)
+@pytest.mark.parametrize("gamma", [0.0, 1.0, 1.5, 2.0])
+@pytest.mark.parametrize("alpha", [0.25, -1.0])
+@pytest.mark.parametrize("sigma", [8.0, 16.0])
+def test_deep_tail_logits_device_and_host_match_definition(sigma, alpha, gamma, dtype):
+    """logits of sigma 8 and 16: most sigmoids saturated, the tails that matched_focal_arith.h keeps cancellation-free
+    (the float64 definition is cancellation-free as well: tests/matched_focal_loss_cases.py::elementwise_stable)"""
+    inp = deep_tail_case(dtype, sigma, device=DEV)
+    compare(inp, f"sigma {sigma} {name(dtype)}/a{alpha}/g{gamma}", alpha=alpha, gamma=gamma)
