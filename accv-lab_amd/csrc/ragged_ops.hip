@@ -101,6 +101,7 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const RaggedDesc d, cons
     long long j;
     int v0, lanes;
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;
+    int* const err = v0 == 0 ? d.err : nullptr;   // one lane of a row counts its out-of-range index, not every lane
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
         // the count (uniform: scalar load) and the index of this slot are fetched together; slots behind the count hold
         // anything (the reference fills them with out-of-range junk) and are never interpreted
@@ -110,18 +111,18 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const RaggedDesc d, cons
         if (j >= load_index(d.counts, i, d.counts_i64)) continue;
         long long from, to;
         if (MODE == kGather) {
-            const long long s = wrap_index(a, d.w_src, d.err);
+            const long long s = wrap_index(a, d.w_src, err);
             if (s < 0) continue;
             from = (i * d.w_src + s) * d.row_vecs;
             to = (i * d.w_idx + j) * d.row_vecs;
         } else if (MODE == kScatter) {
-            const long long o = wrap_index(a, d.w_dst, d.err);
+            const long long o = wrap_index(a, d.w_dst, err);
             if (o < 0) continue;
             from = (i * d.w_idx + j) * d.row_vecs;
             to = (i * d.w_dst + o) * d.row_vecs;
         } else {
-            const long long s = wrap_index(a, d.w_src, d.err);
-            const long long o = wrap_index(b, d.w_dst, d.err);
+            const long long s = wrap_index(a, d.w_src, err);
+            const long long o = wrap_index(b, d.w_dst, err);
             if (s < 0 || o < 0) continue;
             from = (i * d.w_src + s) * d.row_vecs;
             to = (i * d.w_dst + o) * d.row_vecs;
@@ -142,10 +143,11 @@ __global__ __launch_bounds__(256) void gather_fill_kernel(const RaggedDesc d, co
     long long j;
     int v0, lanes;
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;
+    int* const err = v0 == 0 ? d.err : nullptr;   // one lane of a row counts its out-of-range index, not every lane
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
         const long long a = load_index(d.idx_a, i * d.idx_stride + j, d.idx_i64);
         long long s = -1;
-        if (j < load_index(d.counts, i, d.counts_i64)) s = wrap_index(a, d.w_src, d.err);
+        if (j < load_index(d.counts, i, d.counts_i64)) s = wrap_index(a, d.w_src, err);
         const long long from = (i * d.w_src + max(s, 0ll)) * d.row_vecs, to = (i * d.w_idx + j) * d.row_vecs;
         for (long long v = v0; v < d.row_vecs; v += lanes) dst[to + v] = s >= 0 ? src[from + v] : pattern;
     }
@@ -161,10 +163,11 @@ __global__ __launch_bounds__(256) void insert_const_kernel(const RaggedDesc d, c
     long long j;
     int v0, lanes;
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;
+    int* const err = v0 == 0 ? d.err : nullptr;   // one lane of a row counts its out-of-range index, not every lane
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
         const long long a = load_index(d.idx_a, i * d.idx_stride + j, d.idx_i64);
         if (j >= load_index(d.counts, i, d.counts_i64)) continue;
-        const long long o = wrap_index(a, d.w_dst, d.err);
+        const long long o = wrap_index(a, d.w_dst, err);
         if (o < 0) continue;
         const long long to = (i * d.w_dst + o) * d.row_vecs;
         for (long long v = v0; v < d.row_vecs; v += lanes) dst[to + v] = pattern;
@@ -219,6 +222,7 @@ __global__ __launch_bounds__(256) void accumulate_rows_kernel(const RaggedDesc d
     long long j;
     int v0, lanes;
     if (!row_of_thread(g, d.w_idx, j, v0, lanes)) return;   // row_vecs == elements per row here
+    int* const err = v0 == 0 ? d.err : nullptr;   // one lane of a row counts its out-of-range index, not every lane
     for (long long i = blockIdx.y; i < d.batch; i += gridDim.y) {
         const long long slot = i * d.idx_stride + j;
         const long long a = load_index(d.idx_a, slot, d.idx_i64);
@@ -226,12 +230,12 @@ __global__ __launch_bounds__(256) void accumulate_rows_kernel(const RaggedDesc d
         if (j >= load_index(d.counts, i, d.counts_i64)) continue;
         long long s_row, o;
         if (pairs) {
-            const long long s = wrap_index(a, d.w_src, d.err);
-            o = wrap_index(b, d.w_dst, d.err);
+            const long long s = wrap_index(a, d.w_src, err);
+            o = wrap_index(b, d.w_dst, err);
             if (s < 0 || o < 0) continue;
             s_row = (i * d.w_src + s) * d.row_vecs;
         } else {
-            o = wrap_index(a, d.w_dst, d.err);
+            o = wrap_index(a, d.w_dst, err);
             if (o < 0) continue;
             s_row = (i * d.w_idx + j) * d.row_vecs;
         }

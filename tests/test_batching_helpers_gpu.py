@@ -343,7 +343,9 @@ def test_error_behaviour_matches_reference():
 ])
 def test_row_kernels_launch_geometry_extremes(batch, width, k, inner, dtype):
     """the division-free 2-D launch geometry of the ragged byte movers (slot group x sample, 2^k lanes per row) at its
-    corners, for gather (+fill), scatter, pair mapping, pad fill and pack, bit-exact against the oracle"""
+    corners, for `gather_rows`, `scatter_rows`, the pad fill and (up to 1000 samples) `pack_rows`, bit-exact against the
+    oracle.  Gather-fill, pair mapping, constant insert, accumulate and the unpack direction are not run here:
+    test_h2_partition_edges_gpu.py crosses the same corners, and the ones this list leaves out, for every entry point"""
     from accvlab.batching_helpers import batched_indexing_access_cuda as ext
 
     g = np.random.RandomState(batch % 1000 + width)
