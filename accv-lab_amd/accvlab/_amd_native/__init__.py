@@ -78,6 +78,9 @@ RN_MAX_TASKS = 8
 RN_MAX_N = 1024
 RN_MIN_D = 7
 RN_MAX_D = 16
+VB_MAX_BOXES = 256
+VB_COUNTS_I64 = 1
+VB_HW_I64 = 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -184,6 +187,9 @@ SIGNATURES = {
                                        _vp]),
     "accv_center_point_targets_host": (_i, [_vp, _vp, _vp, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
+    # visible-box selection (params: a VisibleBoxesParams by address; out is bool bytes [B, G])
+    "accv_visible_boxes": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp]),
+    "accv_visible_boxes_host": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp]),
     # centre-point decoding with circle NMS (params: a CenterPointDecodeParams by address; outputs [T, B, M, ...])
     "accv_center_point_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_center_point_decode_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -261,6 +267,12 @@ class CenterPointTargetsParams(ctypes.Structure):
                 ("class_pos", ctypes.c_ubyte * 64)]
 
 
+class VisibleBoxesParams(ctypes.Structure):
+    """accv_visible_boxes_params of include/accv_hip.h"""
+    _fields_ = [("minimum_size", ctypes.c_double), ("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong),
+                ("check_occlusion", ctypes.c_int), ("check_size", ctypes.c_int), ("shrink_to_int", ctypes.c_int)]
+
+
 class CenterPointDecodeParams(ctypes.Structure):
     """accv_center_point_decode_params of include/accv_hip.h"""
     _fields_ = [("scores", ctypes.c_void_p * 8), ("indices", ctypes.c_void_p * 8), ("classes", ctypes.c_void_p * 8),
@@ -298,7 +310,7 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
              "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host",
-             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host"}
+             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host"}
 
 
 def _fast_entry(fn, res, args):

@@ -16,7 +16,9 @@ front of that path: ``center_point_targets`` (raw ragged 3D boxes -> centres, ra
 indices of every task of a CenterPoint head in one launch), and its inverse at the end of the path:
 ``center_point_decode`` (the peaks and regression maps of every task -> filtered, circle-NMS'd, compacted boxes, scores
 and labels in one launch), and the other NMS of those heads after it: ``rotated_nms_bev`` (rotated BEV-IoU NMS of every
-task's detections in one launch) over ``rotated_iou_bev`` (the pairwise rotated IoU of two ragged BEV box sets).
+task's detections in one launch) over ``rotated_iou_bev`` (the pairwise rotated IoU of two ragged BEV box sets).  Ahead of
+the 2D target chain: ``visible_bbox_mask`` / ``select_visible_bboxes`` (which boxes of a camera image are drawn at all: the
+occlusion and minimum-size test of the reference's VisibleBboxSelector in one launch, without a canvas).
 """
 from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
@@ -27,10 +29,11 @@ from .lanes import (draw_polylines_batched, draw_polylines_multiscale, draw_targ
 from .ops import draw_heatmap, draw_heatmap_batched, draw_heatmap_multiscale, get_centers_and_radii
 from .peaks import HeatmapPeaks, heatmap_peaks
 from .rotated_nms import rotated_iou_bev, rotated_nms_bev
+from .visible_boxes import select_visible_bboxes, visible_bbox_mask
 
 __version__ = "0.1.0"
 __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_and_radii", "draw_polylines_batched",
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
            "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
            "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
-           "rotated_nms_bev"]
+           "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes"]

@@ -448,6 +448,47 @@ int accv_center_point_targets_host(const float* boxes, const void* labels, const
                                    const accv_center_point_targets_params* params, int* centers, int* radii,
                                    int* out_labels, float* targets, long long* indices, int* source, long long* out_sizes);
 
+/* ------------------------------------------------------------------------------------------------ visible-box selection
+ * Which 2D boxes of a camera image are drawn at all: the occlusion test and the minimum-size test of the reference's
+ * VisibleBboxSelector step (packages/dali_pipeline_framework/.../processing_steps/visible_bbox_selector.py; the operators
+ * check_bbox_visibiity / check_minimum_bbox_size, operators_impl/numba_operators/numba_operators.py:240-403; wired at
+ * examples/pipeline_setup/stream_petr_pipeline.py:397-452) for a ragged batch in ONE launch and without the reference's
+ * H x W canvas.
+ *
+ * boxes: f32 [B, G, 4] contiguous, rows (x1, y1, x2, y2) with the corners in either order; depths: f32 [B, G], smaller is
+ * nearer, needed with check_occlusion; counts [B] int32 (int64 with ACCV_VB_COUNTS_I64), clamped to [0, G]: only slots
+ * below it are read.  image_hw: null (every frame is params->image_h x image_w) or [B, 2] int32 (int64 with
+ * ACCV_VB_HW_I64) rows (H, W), read where the boxes are; either way H and W are clamped to [0, 2^24].  Per frame, in
+ * float32 (written out in csrc/visible_boxes_arith.h):
+ *   painted     corners ordered, lower edges floor and upper edges ceil (ceil and floor with shrink_to_int), each rounded
+ *               edge clamped to [-1, W + 1] / [-1, H + 1]; a box with lo_x > W, hi_x < 0, lo_y > H, hi_y < 0 or a NaN
+ *               coordinate paints nothing; the rest paints its clip to the image, the half-open [x0, x1) x [y0, y1)
+ *   order       np.argsort(-depth, kind="stable"), last painted on top: j above i iff depth_j < depth_i, or equal and
+ *               j > i; -0.0 == 0.0; a NaN depth lies above every number, two NaNs tie
+ *   occlusion   true iff some pixel of the painted rectangle is in the painted rectangle of no box above
+ *   size        raw coordinates clipped to [0, W] / [0, H]; |x2 - x1| >= (float)minimum_size and |y2 - y1| likewise (NaN
+ *               fails); a box that fails still occludes
+ * out: bool bytes [B, G], the AND of the requested checks, 0 in the slots from counts[b] on: every byte is written.  One
+ * workgroup per frame, memory independent of H and W, no atomics, no host synchronisation, bitwise reproducible.  B == 0 or
+ * G == 0 launches nothing.  Returns ACCV_EINVAL (null params, negative size, unknown flags, neither check requested,
+ * G > ACCV_VB_MAX_BOXES, null or misaligned pointers, occlusion without depths) before touching the device, ACCV_ELAUNCH if
+ * the launch fails.  accv_visible_boxes_host runs the same integer algorithm serially on host memory. */
+#define ACCV_VB_MAX_BOXES 256
+#define ACCV_VB_COUNTS_I64 1u
+#define ACCV_VB_HW_I64 2u
+typedef struct accv_visible_boxes_params {
+    double minimum_size;       /* used with check_size */
+    long long image_h, image_w; /* used when image_hw is null */
+    int check_occlusion;
+    int check_size;
+    int shrink_to_int;
+} accv_visible_boxes_params;
+int accv_visible_boxes(const float* boxes, const float* depths, const void* counts, const void* image_hw, unsigned flags,
+                       long long B, long long G, const accv_visible_boxes_params* params, unsigned char* out, void* stream);
+int accv_visible_boxes_host(const float* boxes, const float* depths, const void* counts, const void* image_hw,
+                            unsigned flags, long long B, long long G, const accv_visible_boxes_params* params,
+                            unsigned char* out);
+
 /* ------------------------------------------------------------------------------------------------ centre-point decoding
  * The prediction side of a centre-point head, the inverse of accv_center_point_targets: mmdet3d's
  * CenterPointBBoxCoder.decode (core/bbox/coders/centerpoint_bbox_coders.py: the gathers, exp, atan2, the affine map back
