@@ -18,12 +18,14 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _amd_native as _nat
+from . import _matched_pairs as _mp
 from .ragged import RaggedBatch
 
 __all__ = ["matched_box_loss"]
 
 _WHO = "matched_box_loss"
-_DTYPES = _nat.FLOAT_DTYPE_CODES
+_STEM = "accv_matched_box_loss"
+_DTYPES = _mp.DTYPES
 _IOU_KINDS = {None: _nat.MB_IOU_NONE, "iou": _nat.MB_IOU, "giou": _nat.MB_GIOU}
 _FORMATS = {"xyxy": 0, "cxcywh": _nat.MB_CXCYWH}
 
@@ -38,7 +40,7 @@ class _Call:
         self.B, self.Q, self.D = (int(v) for v in boxes.shape)
         self.G, self.K = int(gt.shape[1]), int(pind.shape[1])
         self.flags = flags
-        self.out_dtype = torch.float64 if boxes.dtype == torch.float64 else torch.float32
+        self.out_dtype = _mp.out_dtype(boxes.dtype)
 
     def inputs(self, boxes, gt, pind, gind, counts, weights, cw_dev):
         """the pointer arguments; the optional operands go into the parameter struct"""
@@ -59,22 +61,9 @@ class _MatchedBoxLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, call, boxes, gt, pind, gind, counts, weights, cw_dev):
-        dev = call.dev
         tensors = (boxes, gt, pind, gind, counts, weights, cw_dev)
         run = call.B * call.Q * call.K > 0
-        out = (torch.empty if run else torch.zeros)((2, call.B), dtype=call.out_dtype, device=dev)
-        denom = torch.empty((), dtype=torch.float64, device=dev)
-        if run:
-            lib = _nat.lib()
-            if dev.type == "cuda":
-                nbytes = lib.accv_matched_box_loss_workspace_bytes(call.B, call.Q, call.D)
-                ws = _nat.workspace(nbytes, dev)
-                with _nat.device_guard(dev):
-                    _nat.check(lib.accv_matched_box_loss(*call.inputs(*tensors), *call.shape(boxes), out.data_ptr(),
-                                                         denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
-            else:
-                _nat.check(lib.accv_matched_box_loss_host(*call.inputs(*tensors), *call.shape(boxes), out.data_ptr(),
-                                                          denom.data_ptr()), _WHO)
+        out, denom = _mp.run_forward(_WHO, _STEM, call, tensors, run, 2, (call.B, call.Q, call.D))
         ctx.call, ctx.run = call, run
         # everything the backward kernel reads: alive until then, and guarded by torch's version check
         ctx.save_for_backward(denom, *tensors)
@@ -91,35 +80,7 @@ class _MatchedBoxLoss(torch.autograd.Function):
             return (None,) * 8
         if not ctx.run:   # no pair anywhere: nothing depends on the boxes
             return (None, torch.zeros(boxes.shape, dtype=boxes.dtype, device=call.dev)) + (None,) * 6
-        grad = torch.empty(boxes.shape, dtype=boxes.dtype, device=call.dev)   # contiguous, written completely
-        grad_l1 = None if grad_l1 is None else grad_l1.to(call.out_dtype).contiguous()
-        grad_iou = None if grad_iou is None else grad_iou.to(call.out_dtype).contiguous()
-        lib = _nat.lib()
-        args = (*call.inputs(*tensors), None if grad_l1 is None else grad_l1.data_ptr(),   # re-points the struct
-                None if grad_iou is None else grad_iou.data_ptr(), denom.data_ptr(), *call.shape(boxes), grad.data_ptr())
-        if call.dev.type == "cuda":
-            with _nat.device_guard(call.dev):
-                _nat.check(lib.accv_matched_box_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
-        else:
-            _nat.check(lib.accv_matched_box_loss_bwd_host(*args), _WHO + " backward")
-        return (None, grad) + (None,) * 6
-
-
-def _ragged(name, rb, what, dims):
-    if not isinstance(rb, RaggedBatch):
-        raise TypeError(f"{_WHO}: {name} must be a RaggedBatch {what}, got {type(rb).__name__}")
-    t = rb.tensor
-    if rb.num_batch_dims != 1 or t.dim() != dims or rb.non_uniform_dim != 1:
-        raise ValueError(f"{_WHO}: {name} must be a RaggedBatch {what} with non_uniform_dim 1, got shape {tuple(t.shape)}, "
-                         f"non_uniform_dim {rb.non_uniform_dim}")
-    return t.detach().contiguous()
-
-
-def _index(name, rb):
-    t = _ragged(name, rb, "[B, K]", 2)
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{_WHO}: {name} must be int32 or int64, got {t.dtype}")
-    return t
+        return (None, _mp.run_backward(_WHO, _STEM, call, tensors, (grad_l1, grad_iou), denom)) + (None,) * 6
 
 
 def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: RaggedBatch, gt_ind: RaggedBatch, *,
@@ -180,23 +141,12 @@ def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: 
     Special values: a NaN in a matched prediction makes its frame's sums and that query's gradient NaN (with an IoU kind
     all four components, otherwise the component of the NaN coordinate); rows of unmatched queries are never read.
     """
-    if not isinstance(pred_boxes, torch.Tensor):
-        raise TypeError(f"{_WHO}: pred_boxes must be a tensor, got {type(pred_boxes).__name__}")
-    if pred_boxes.dim() != 3:
-        raise ValueError(f"{_WHO}: pred_boxes must be [B, Q, D], got shape {tuple(pred_boxes.shape)}")
-    if pred_boxes.dtype not in _DTYPES:
-        raise TypeError(f"{_WHO}: pred_boxes must be float32, float16, bfloat16 or float64, got {pred_boxes.dtype}")
-    if pred_boxes.shape[-1] > 1 and pred_boxes.stride(-1) != 1:
-        raise ValueError(f"{_WHO}: the last dimension of pred_boxes must have unit stride, got stride "
-                         f"{pred_boxes.stride(-1)}")
+    _mp.dense(_WHO, "pred_boxes", pred_boxes, "[B, Q, D]")
     dev = pred_boxes.device
-    if dev.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: unsupported device {dev}")
     B, Q, D = (int(v) for v in pred_boxes.shape)
     if not 1 <= D <= _nat.MB_MAX_D:
         raise ValueError(f"{_WHO}: needs 1 <= D <= {_nat.MB_MAX_D}, got D = {D}")
-    if Q > 1 and pred_boxes.stride(1) < D or B > 1 and pred_boxes.stride(0) < 0:
-        raise ValueError(f"{_WHO}: overlapping or reversed pred_boxes (strides {pred_boxes.stride()}) are not supported")
+    _mp.not_overlapping(_WHO, "pred_boxes", pred_boxes, D)
     if box_format not in _FORMATS:
         raise ValueError(f"{_WHO}: box_format must be 'xyxy' or 'cxcywh', got {box_format!r}")
     if iou_kind not in _IOU_KINDS:
@@ -207,28 +157,13 @@ def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: 
     if not iou_eps >= 0.0:
         raise ValueError(f"{_WHO}: iou_eps must be >= 0, got {iou_eps}")
 
-    gt = _ragged("gt_boxes", gt_boxes, "[B, G*, D]", 3)
+    gt = _mp.ragged(_WHO, "gt_boxes", gt_boxes, "[B, G*, D]", 3)
     if gt.dtype != pred_boxes.dtype:
         raise TypeError(f"{_WHO}: gt_boxes is {gt.dtype}, pred_boxes {pred_boxes.dtype}")
     if int(gt.shape[2]) != D:
         raise ValueError(f"{_WHO}: gt_boxes has {gt.shape[2]} coordinates, pred_boxes {D}")
-    pind = _index("pred_ind", pred_ind)
-    gind = _index("gt_ind", gt_ind)
-    if pind.dtype != gind.dtype:
-        raise TypeError(f"{_WHO}: pred_ind is {pind.dtype}, gt_ind {gind.dtype}: one index dtype expected")
-    if pind.shape != gind.shape:
-        raise ValueError(f"{_WHO}: pred_ind has shape {tuple(pind.shape)}, gt_ind {tuple(gind.shape)}")
-    sizes = pred_ind.sample_sizes
-    if sizes.dim() != 1 or sizes.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{_WHO}: pred_ind.sample_sizes must be int32 or int64 [B]")
-    weights = query_weights
-    if weights is not None:
-        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (B, Q):
-            raise ValueError(f"{_WHO}: query_weights must be a tensor [B, Q] = [{B}, {Q}], got "
-                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
-        if weights.dtype != pred_boxes.dtype:
-            raise TypeError(f"{_WHO}: query_weights is {weights.dtype}, pred_boxes {pred_boxes.dtype}")
-        weights = weights.detach().contiguous()
+    pind, gind, counts = _mp.match_indices(_WHO, pred_ind, gt_ind)
+    weights = _mp.query_weights(_WHO, query_weights, pred_boxes, "pred_boxes")
     cw_dev, cw_values = None, None
     if isinstance(code_weights, torch.Tensor):
         if tuple(code_weights.shape) != (D,):
@@ -246,17 +181,10 @@ def matched_box_loss(pred_boxes: torch.Tensor, gt_boxes: RaggedBatch, pred_ind: 
                             f"{type(code_weights).__name__}") from None
         if len(cw_values) != D:
             raise ValueError(f"{_WHO}: code_weights must have shape [{D}], got {len(cw_values)} values")
-    for name, t in (("gt_boxes", gt), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", sizes),
-                    ("query_weights", weights)):
-        if t is None:
-            continue
-        if t.device != dev:
-            raise ValueError(f"{_WHO}: {name} is on {t.device}, pred_boxes on {dev}")
-        if int(t.shape[0]) != B:
-            raise ValueError(f"{_WHO}: {name} has batch size {t.shape[0]}, pred_boxes {B}")
+    _mp.same_place(_WHO, dev, B, (("gt_boxes", gt), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", counts),
+                                  ("query_weights", weights)), ref="pred_boxes")
 
     mode, value, avg_dev = _nat.avg_factor_args(avg_factor, dev, _WHO, ValueError, "the boxes' device")
-    counts = sizes.detach().to(torch.int64).contiguous()
     params = _nat.MatchedBoxParams()
     params.iou_eps, params.avg_factor, params.avg_mode, params.iou_kind = iou_eps, value, mode, _IOU_KINDS[iou_kind]
     for d in range(D):

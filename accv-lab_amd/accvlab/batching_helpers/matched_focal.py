@@ -18,12 +18,14 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _amd_native as _nat
+from . import _matched_pairs as _mp
 from .ragged import RaggedBatch
 
 __all__ = ["matched_focal_loss"]
 
 _WHO = "matched_focal_loss"
-_DTYPES = _nat.FLOAT_DTYPE_CODES
+_STEM = "accv_matched_focal_loss"
+_DTYPES = _mp.DTYPES
 _PARAMS = {}   # (alpha, gamma, mode, value) -> MatchedFocalParams without a device pointer
 
 
@@ -50,7 +52,7 @@ class _Call:
         self.G, self.K = int(labels.shape[1]), int(pind.shape[1])
         self.flags = (_nat.MF_IDX_I64 if pind.dtype == torch.int64 else 0) | \
                      (_nat.MF_LABELS_I64 if labels.dtype == torch.int64 else 0)
-        self.out_dtype = torch.float64 if logits.dtype == torch.float64 else torch.float32
+        self.out_dtype = _mp.out_dtype(logits.dtype)
 
     @staticmethod
     def inputs(logits, labels, pind, gind, counts, weights):
@@ -68,22 +70,8 @@ class _Call:
 class _MatchedFocalLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, call, logits, labels, pind, gind, counts, weights):
-        dev = call.dev
         tensors = (logits, labels, pind, gind, counts, weights)
-        n = call.B * call.Q * call.C
-        out = (torch.empty if n > 0 else torch.zeros)((call.B,), dtype=call.out_dtype, device=dev)
-        denom = torch.empty((), dtype=torch.float64, device=dev)
-        if n > 0:
-            lib = _nat.lib()
-            if dev.type == "cuda":
-                nbytes = lib.accv_matched_focal_loss_workspace_bytes(call.B, call.Q, call.C)
-                ws = _nat.workspace(nbytes, dev)
-                with _nat.device_guard(dev):
-                    _nat.check(lib.accv_matched_focal_loss(*call.inputs(*tensors), *call.shape(logits), out.data_ptr(),
-                                                           denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)), _WHO)
-            else:
-                _nat.check(lib.accv_matched_focal_loss_host(*call.inputs(*tensors), *call.shape(logits), out.data_ptr(),
-                                                            denom.data_ptr()), _WHO)
+        out, denom = _mp.run_forward(_WHO, _STEM, call, tensors, call.B * call.Q * call.C > 0, 1, (call.B, call.Q, call.C))
         ctx.call = call
         # everything the backward kernel reads: alive until then, and guarded by torch's version check
         ctx.save_for_backward(denom, *tensors)
@@ -97,29 +85,9 @@ class _MatchedFocalLoss(torch.autograd.Function):
         logits = tensors[0]
         if not ctx.needs_input_grad[1]:
             return (None,) * 7
-        grad = torch.empty(logits.shape, dtype=logits.dtype, device=call.dev)   # contiguous, written completely
-        if grad.numel() > 0:
-            grad_out = grad_out.to(call.out_dtype).contiguous()
-            lib = _nat.lib()
-            args = (*call.inputs(*tensors), grad_out.data_ptr(), denom.data_ptr(), *call.shape(logits), grad.data_ptr())
-            if call.dev.type == "cuda":
-                with _nat.device_guard(call.dev):
-                    _nat.check(lib.accv_matched_focal_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
-            else:
-                _nat.check(lib.accv_matched_focal_loss_bwd_host(*args), _WHO + " backward")
-        return None, grad, None, None, None, None, None
-
-
-def _ragged(name, rb, what):
-    if not isinstance(rb, RaggedBatch):
-        raise TypeError(f"{_WHO}: {name} must be a RaggedBatch {what}, got {type(rb).__name__}")
-    t = rb.tensor
-    if rb.num_batch_dims != 1 or t.dim() != 2 or rb.non_uniform_dim != 1:
-        raise ValueError(f"{_WHO}: {name} must be a RaggedBatch {what} with non_uniform_dim 1, got shape {tuple(t.shape)}, "
-                         f"non_uniform_dim {rb.non_uniform_dim}")
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{_WHO}: {name} must be int32 or int64, got {t.dtype}")
-    return t.detach().contiguous()
+        if logits.numel() == 0:
+            return (None, torch.empty(logits.shape, dtype=logits.dtype, device=call.dev)) + (None,) * 5
+        return (None, _mp.run_backward(_WHO, _STEM, call, tensors, (grad_out,), denom)) + (None,) * 5
 
 
 def matched_focal_loss(pred_logits: torch.Tensor, gt_labels: RaggedBatch, pred_ind: RaggedBatch, gt_ind: RaggedBatch, *,
@@ -179,55 +147,22 @@ def matched_focal_loss(pred_logits: torch.Tensor, gt_labels: RaggedBatch, pred_i
     ``+inf`` and ``-alpha`` as a positive, 0 and 0 as a negative (the limits; the float64 composition has ``inf * 0``
     there).
     """
-    if not isinstance(pred_logits, torch.Tensor):
-        raise TypeError(f"{_WHO}: pred_logits must be a tensor, got {type(pred_logits).__name__}")
-    if pred_logits.dim() != 3:
-        raise ValueError(f"{_WHO}: pred_logits must be [B, Q, C], got shape {tuple(pred_logits.shape)}")
-    if pred_logits.dtype not in _DTYPES:
-        raise TypeError(f"{_WHO}: pred_logits must be float32, float16, bfloat16 or float64, got {pred_logits.dtype}")
-    if pred_logits.shape[-1] > 1 and pred_logits.stride(-1) != 1:
-        raise ValueError(f"{_WHO}: the last dimension of pred_logits must have unit stride, got stride "
-                         f"{pred_logits.stride(-1)}")
+    _mp.dense(_WHO, "pred_logits", pred_logits, "[B, Q, C]")
     dev = pred_logits.device
-    if dev.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: unsupported device {dev}")
-    B, Q, C = (int(v) for v in pred_logits.shape)
-    if Q > 1 and C > 0 and pred_logits.stride(1) < C or B > 1 and pred_logits.stride(0) < 0:
-        raise ValueError(f"{_WHO}: overlapping or reversed pred_logits (strides {pred_logits.stride()}) are not supported")
+    _mp.not_overlapping(_WHO, "pred_logits", pred_logits, int(pred_logits.shape[2]))
     alpha, gamma = float(alpha), float(gamma)
     if not gamma >= 0.0:
         raise ValueError(f"{_WHO}: gamma must be >= 0, got {gamma}")
     if alpha != alpha:
         raise ValueError(f"{_WHO}: alpha is NaN")
 
-    labels = _ragged("gt_labels", gt_labels, "[B, G*]")
-    pind = _ragged("pred_ind", pred_ind, "[B, K]")
-    gind = _ragged("gt_ind", gt_ind, "[B, K]")
-    if pind.dtype != gind.dtype:
-        raise TypeError(f"{_WHO}: pred_ind is {pind.dtype}, gt_ind {gind.dtype}: one index dtype expected")
-    if pind.shape != gind.shape:
-        raise ValueError(f"{_WHO}: pred_ind has shape {tuple(pind.shape)}, gt_ind {tuple(gind.shape)}")
-    sizes = pred_ind.sample_sizes
-    if sizes.dim() != 1 or sizes.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{_WHO}: pred_ind.sample_sizes must be int32 or int64 [B]")
-    weights = query_weights
-    if weights is not None:
-        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (B, Q):
-            raise ValueError(f"{_WHO}: query_weights must be a tensor [B, Q] = [{B}, {Q}], got "
-                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
-        if weights.dtype != pred_logits.dtype:
-            raise TypeError(f"{_WHO}: query_weights is {weights.dtype}, pred_logits {pred_logits.dtype}")
-        weights = weights.detach().contiguous()
-    for name, t in (("gt_labels", labels), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", sizes),
-                    ("query_weights", weights)):
-        if t is None:
-            continue
-        if t.device != dev:
-            raise ValueError(f"{_WHO}: {name} is on {t.device}, pred_logits on {dev}")
-        if int(t.shape[0]) != B:
-            raise ValueError(f"{_WHO}: {name} has batch size {t.shape[0]}, pred_logits {B}")
+    labels = _mp.index(_WHO, "gt_labels", gt_labels, "[B, G*]")
+    pind, gind, counts = _mp.match_indices(_WHO, pred_ind, gt_ind)
+    weights = _mp.query_weights(_WHO, query_weights, pred_logits, "pred_logits")
+    _mp.same_place(_WHO, dev, int(pred_logits.shape[0]), (("gt_labels", labels), ("pred_ind", pind), ("gt_ind", gind),
+                                                            ("pred_ind.sample_sizes", counts), ("query_weights", weights)),
+                   ref="pred_logits")
 
     mode, value, avg_dev = _nat.avg_factor_args(avg_factor, dev, _WHO, ValueError, "the logits' device")
-    counts = sizes.detach().to(torch.int64).contiguous()
     call = _Call(pred_logits, labels, pind, _params(alpha, gamma, mode, value, avg_dev), avg_dev)
     return _MatchedFocalLoss.apply(call, pred_logits, labels, pind, gind, counts, weights)

@@ -27,36 +27,20 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ... import _amd_native as _nat
+from ...batching_helpers import _matched_pairs as _mp
 from ...batching_helpers.assignment import batched_linear_sum_assignment
 from ...batching_helpers.ragged import RaggedBatch
 
 __all__ = ["batched_polyline_matching_cost", "batched_polyline_hungarian_match", "matched_polyline_loss"]
 
-_DTYPES = _nat.FLOAT_DTYPE_CODES
+_DTYPES = _mp.DTYPES
 _KINDS = {"one_minus_prob": _nat.MC_ONE_MINUS_PROB, "neg_prob": _nat.MC_NEG_PROB, "focal": _nat.MC_FOCAL}
 _CLOSED_FLAGS = {torch.bool: 0, torch.uint8: 0, torch.int32: _nat.PM_CLOSED_I32, torch.int64: _nat.PM_CLOSED_I64}
 
 
-def _ragged(who, name, rb, what, dims):
-    if not isinstance(rb, RaggedBatch):
-        raise TypeError(f"{who}: {name} must be a RaggedBatch {what}, got {type(rb).__name__}")
-    t = rb.tensor
-    if rb.num_batch_dims != 1 or t.dim() != dims or rb.non_uniform_dim != 1:
-        raise ValueError(f"{who}: {name} must be a RaggedBatch {what} with non_uniform_dim 1, got shape {tuple(t.shape)}, "
-                         f"non_uniform_dim {rb.non_uniform_dim}")
-    return t.detach().contiguous()
-
-
 def _lines(who, pred_lines, gt_lines):
     """-> (gt tensor, B, Q, G, P, D, stride_b, stride_q) of validated lines"""
-    if not isinstance(pred_lines, torch.Tensor):
-        raise TypeError(f"{who}: pred_lines must be a tensor, got {type(pred_lines).__name__}")
-    if pred_lines.dim() != 4:
-        raise ValueError(f"{who}: pred_lines must be [B, Q, P, D], got shape {tuple(pred_lines.shape)}")
-    if pred_lines.dtype not in _DTYPES:
-        raise TypeError(f"{who}: pred_lines must be float32, float16, bfloat16 or float64, got {pred_lines.dtype}")
-    if pred_lines.device.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{who}: unsupported device {pred_lines.device}")
+    _mp.dense(who, "pred_lines", pred_lines, "[B, Q, P, D]", unit_stride=False)
     B, Q, P, D = (int(v) for v in pred_lines.shape)
     if not _nat.PM_MIN_P <= P <= _nat.PM_MAX_P:
         raise ValueError(f"{who}: needs {_nat.PM_MIN_P} <= P <= {_nat.PM_MAX_P}, got P = {P}")
@@ -64,9 +48,8 @@ def _lines(who, pred_lines, gt_lines):
         raise ValueError(f"{who}: needs D of 2 or 3, got D = {D}")
     if pred_lines.stride(3) != 1 or pred_lines.stride(2) != D:
         raise ValueError(f"{who}: the last two dimensions of pred_lines must be contiguous, got strides {pred_lines.stride()}")
-    if Q > 1 and pred_lines.stride(1) < P * D or B > 1 and pred_lines.stride(0) < 0:
-        raise ValueError(f"{who}: overlapping or reversed pred_lines (strides {pred_lines.stride()}) are not supported")
-    gt = _ragged(who, "gt_lines", gt_lines, "[B, G*, P, D]", 4)
+    _mp.not_overlapping(who, "pred_lines", pred_lines, P * D)
+    gt = _mp.ragged(who, "gt_lines", gt_lines, "[B, G*, P, D]", 4)
     if gt.dtype != pred_lines.dtype:
         raise TypeError(f"{who}: gt_lines is {gt.dtype}, pred_lines {pred_lines.dtype}")
     if tuple(gt.shape[2:]) != (P, D):
@@ -81,7 +64,7 @@ def _closed(who, gt_closed, gt_lines, B, G, dev):
     """-> (tensor or None, flag)"""
     if gt_closed is None:
         return None, 0
-    t = _ragged(who, "gt_closed", gt_closed, "[B, G*]", 2)
+    t = _mp.ragged(who, "gt_closed", gt_closed, "[B, G*]", 2)
     if t.dtype not in _CLOSED_FLAGS:
         raise TypeError(f"{who}: gt_closed must be bool, uint8, int32 or int64, got {t.dtype}")
     if tuple(t.shape) != (B, G):
@@ -89,16 +72,6 @@ def _closed(who, gt_closed, gt_lines, B, G, dev):
     if t.device != dev:
         raise ValueError(f"{who}: gt_closed is on {t.device}, pred_lines on {dev}")
     return t, _CLOSED_FLAGS[t.dtype]
-
-
-def _same_place(who, dev, B, named):
-    for name, t in named:
-        if t is None:
-            continue
-        if t.device != dev:
-            raise ValueError(f"{who}: {name} is on {t.device}, expected {dev}")
-        if int(t.shape[0]) != B:
-            raise ValueError(f"{who}: {name} has batch size {t.shape[0]}, expected {B}")
 
 
 def batched_polyline_matching_cost(pred_lines: Optional[torch.Tensor], gt_lines: Optional[RaggedBatch], pred_scores=None,
@@ -154,9 +127,7 @@ def batched_polyline_matching_cost(pred_lines: Optional[torch.Tensor], gt_lines:
             raise ValueError(f"{who}: the last dimension of pred_scores must have unit stride, got stride "
                              f"{pred_scores.stride(-1)}")
         scores = pred_scores.detach()
-        labels = _ragged(who, "gt_labels", gt_labels, "[B, G*]", 2)
-        if labels.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"{who}: gt_labels must be int32 or int64, got {labels.dtype}")
+        labels = _mp.index(who, "gt_labels", gt_labels, "[B, G*]")
         if gt is None:
             B, Q, G, P, D, sb, sq = int(scores.shape[0]), int(scores.shape[1]), int(labels.shape[1]), 2, 2, 0, 4
             dev, dtype, sizes_rb = scores.device, scores.dtype, gt_labels
@@ -168,8 +139,8 @@ def batched_polyline_matching_cost(pred_lines: Optional[torch.Tensor], gt_lines:
             raise ValueError(f"{who}: pred_scores has shape {tuple(scores.shape)}, expected [{B}, {Q}, C]")
         if int(labels.shape[1]) != G:
             raise ValueError(f"{who}: gt_labels has {labels.shape[1]} objects per frame, expected {G}")
-    _same_place(who, dev, B, (("gt_lines", gt), ("pred_scores", scores), ("gt_labels", labels),
-                              ("sample sizes", sizes_rb.sample_sizes)))
+    _mp.same_place(who, dev, B, (("gt_lines", gt), ("pred_scores", scores), ("gt_labels", labels),
+                                 ("sample sizes", sizes_rb.sample_sizes)))
 
     out = torch.empty((B, Q, G), dtype=torch.float64 if dtype == torch.float64 else torch.float32, device=dev)
     if B * Q * G > 0:
@@ -211,6 +182,7 @@ def batched_polyline_hungarian_match(pred_lines, gt_lines, pred_scores=None, gt_
 
 
 _WHO = "matched_polyline_loss"
+_STEM = "accv_matched_polyline_loss"
 
 
 class _Call:
@@ -223,7 +195,7 @@ class _Call:
         self.B, self.Q, self.G, self.P, self.D = dims
         self.K = int(pind.shape[1])
         self.flags = flags
-        self.out_dtype = torch.float64 if lines.dtype == torch.float64 else torch.float32
+        self.out_dtype = _mp.out_dtype(lines.dtype)
 
     def inputs(self, lines, gt, pind, gind, counts, closed):
         """the pointer arguments; the optional operand goes into the parameter struct"""
@@ -240,23 +212,9 @@ class _MatchedPolylineLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, call, lines, gt, pind, gind, counts, closed):
-        dev = call.dev
         tensors = (lines, gt, pind, gind, counts, closed)
         run = call.B * call.Q * call.K > 0
-        out = (torch.empty if run else torch.zeros)((2, call.B), dtype=call.out_dtype, device=dev)
-        denom = torch.empty((), dtype=torch.float64, device=dev)
-        if run:
-            lib = _nat.lib()
-            if dev.type == "cuda":
-                nbytes = lib.accv_matched_polyline_loss_workspace_bytes(call.B, call.Q)
-                ws = _nat.workspace(nbytes, dev)
-                with _nat.device_guard(dev):
-                    _nat.check(lib.accv_matched_polyline_loss(*call.inputs(*tensors), *call.shape(lines), out.data_ptr(),
-                                                              denom.data_ptr(), ws.data_ptr(), nbytes, _nat.stream_ptr(dev)),
-                               _WHO)
-            else:
-                _nat.check(lib.accv_matched_polyline_loss_host(*call.inputs(*tensors), *call.shape(lines), out.data_ptr(),
-                                                               denom.data_ptr()), _WHO)
+        out, denom = _mp.run_forward(_WHO, _STEM, call, tensors, run, 2, (call.B, call.Q))
         ctx.call, ctx.run = call, run
         # everything the backward kernel reads: alive until then, and guarded by torch's version check
         ctx.save_for_backward(denom, *tensors)
@@ -273,25 +231,7 @@ class _MatchedPolylineLoss(torch.autograd.Function):
             return (None,) * 7
         if not ctx.run:   # no pair anywhere: nothing depends on the lines
             return (None, torch.zeros(lines.shape, dtype=lines.dtype, device=call.dev)) + (None,) * 5
-        grad = torch.empty(lines.shape, dtype=lines.dtype, device=call.dev)   # contiguous, written completely
-        grad_pts = None if grad_pts is None else grad_pts.to(call.out_dtype).contiguous()
-        grad_dir = None if grad_dir is None else grad_dir.to(call.out_dtype).contiguous()
-        lib = _nat.lib()
-        args = (*call.inputs(*tensors), None if grad_pts is None else grad_pts.data_ptr(),   # re-points the struct
-                None if grad_dir is None else grad_dir.data_ptr(), denom.data_ptr(), *call.shape(lines), grad.data_ptr())
-        if call.dev.type == "cuda":
-            with _nat.device_guard(call.dev):
-                _nat.check(lib.accv_matched_polyline_loss_bwd(*args, _nat.stream_ptr(call.dev)), _WHO + " backward")
-        else:
-            _nat.check(lib.accv_matched_polyline_loss_bwd_host(*args), _WHO + " backward")
-        return (None, grad) + (None,) * 5
-
-
-def _index(name, rb):
-    t = _ragged(_WHO, name, rb, "[B, K]", 2)
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{_WHO}: {name} must be int32 or int64, got {t.dtype}")
-    return t
+        return (None, _mp.run_backward(_WHO, _STEM, call, tensors, (grad_pts, grad_dir), denom)) + (None,) * 5
 
 
 def matched_polyline_loss(pred_lines: torch.Tensor, gt_lines: RaggedBatch, pred_ind: RaggedBatch, gt_ind: RaggedBatch, *,
@@ -340,19 +280,10 @@ def matched_polyline_loss(pred_lines: torch.Tensor, gt_lines: RaggedBatch, pred_
     dir_eps = float(dir_eps)
     if not dir_eps >= 0.0:
         raise ValueError(f"{_WHO}: dir_eps must be >= 0, got {dir_eps}")
-    pind = _index("pred_ind", pred_ind)
-    gind = _index("gt_ind", gt_ind)
-    if pind.dtype != gind.dtype:
-        raise TypeError(f"{_WHO}: pred_ind is {pind.dtype}, gt_ind {gind.dtype}: one index dtype expected")
-    if pind.shape != gind.shape:
-        raise ValueError(f"{_WHO}: pred_ind has shape {tuple(pind.shape)}, gt_ind {tuple(gind.shape)}")
-    sizes = pred_ind.sample_sizes
-    if sizes.dim() != 1 or sizes.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{_WHO}: pred_ind.sample_sizes must be int32 or int64 [B]")
-    _same_place(_WHO, dev, B, (("gt_lines", gt), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", sizes)))
+    pind, gind, counts = _mp.match_indices(_WHO, pred_ind, gt_ind)
+    _mp.same_place(_WHO, dev, B, (("gt_lines", gt), ("pred_ind", pind), ("gt_ind", gind), ("pred_ind.sample_sizes", counts)))
 
     mode, value, avg_dev = _nat.avg_factor_args(avg_factor, dev, _WHO, ValueError, "the lines' device")
-    counts = sizes.detach().to(torch.int64).contiguous()
     params = _nat.PolylineMatchParams()
     params.dir_eps, params.avg_factor, params.avg_mode, params.dir_loss = dir_eps, value, mode, 1 if dir_loss else 0
     params.pred_stride_b, params.pred_stride_q = sb, sq

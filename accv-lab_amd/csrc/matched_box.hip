@@ -4,13 +4,13 @@
 //   out[1][b] = sum_pairs w[b, q] * (1 - giou(p, g))  or  (1 - iou(p, g)) / denom          (D == 4; zeros without an IoU kind)
 //
 // The pair of query q in frame b is the LOWEST slot j < clamp(counts[b], 0, K) whose (pred_ind[b, j], gt_ind[b, j]) names q
-// with both indices in range — the rule of matched_focal.hip, so the two losses see the same pairs.  Per-pair arithmetic:
-// matched_box_arith.h.
+// with both indices in range — the rule of matched_pairs.h, which matched_focal.hip reads too, so the two losses see the
+// same pairs.  Per-pair arithmetic: matched_box_arith.h.
 //
 // Forward: a workgroup owns kThreads consecutive queries of one frame.  It builds their query -> slot table in LDS
-// (atomicMin on the slot number in LDS; no global atomics); a lane per query looks its pair up, evaluates both terms and
+// (scan_pairs of matched_pairs.h; no global atomics); a lane per query looks its pair up, evaluates both terms and
 // the workgroup sums them in f64 in a fixed order: one (l1, iou) partial per workgroup in the caller's workspace.  A
-// one-block launch (matched_pair_finish.h) adds each frame's partials in a fixed order, counts the pairs, applies the
+// one-block launch (matched_pairs.h) adds each frame's partials in a fixed order, counts the pairs, applies the
 // denominator and leaves it on the device for the backward.
 // Backward: the same table, then every element of the contiguous [B, Q, D] gradient written exactly once in the boxes'
 // dtype, +0 for a query without a pair: no zero fill, no atomics, no read of the gradient.  D == 4: a lane per query and
@@ -21,12 +21,11 @@
 
 #include <climits>
 #include <cstdint>
-#include <new>
 #include <vector>
 
 #include "accv_common.h"
 #include "matched_box_arith.h"
-#include "matched_pair_finish.h"
+#include "matched_pairs.h"
 
 #pragma clang fp contract(off)
 
@@ -36,7 +35,6 @@ using namespace accv_mb;
 
 constexpr int kThreads = 256;               // and queries per workgroup
 constexpr unsigned kKnownFlags = ACCV_MB_IDX_I64 | ACCV_MB_CXCYWH;
-constexpr int kNoSlot = INT_MAX;
 
 struct Args {
     const void* p;              // [B, Q, D] predictions, element (b, q, d) at b * sb + q * sq + d
@@ -124,34 +122,7 @@ __device__ __forceinline__ void build_table(const Args& a, long long b, long lon
     s_slot[tid] = kNoSlot;
     if (tid < kMaxD) s_cw[tid] = tid < a.D ? code_weight<DT>(a, tid) : typename Compute<DT>::type(0);
     __syncthreads();
-    const long long n = clamp_count(a.counts, b, a.K, 1);
-    for (long long j = tid; j < n; j += kThreads) {
-        long long q, g;   // both indices in ONE branch on their dtype, so the two loads are in flight together
-        if (a.idx64) {
-            q = static_cast<const long long*>(a.pind)[b * a.K + j];
-            g = static_cast<const long long*>(a.gind)[b * a.K + j];
-        } else {
-            q = static_cast<const int*>(a.pind)[b * a.K + j];
-            g = static_cast<const int*>(a.gind)[b * a.K + j];
-        }
-        if (q >= q0 && q < q0 + nq && g >= 0 && g < a.G) atomicMin(&s_slot[(int)(q - q0)], (int)j);
-    }
-    __syncthreads();
-}
-
-// the range of a workgroup: frame, first query, number of queries
-struct Range {
-    long long b, q0;
-    int nq;
-};
-__device__ __forceinline__ Range range_of(const Args& a)
-{
-    Range r;
-    r.b = blockIdx.x / a.nqb;
-    r.q0 = (blockIdx.x - r.b * a.nqb) * kThreads;
-    const long long left = a.Q - r.q0;
-    r.nq = (int)(left < kThreads ? left : kThreads);
-    return r;
+    scan_pairs<kThreads>(a.pind, a.gind, a.idx64, a.counts, b, a.K, a.G, q0, nq, s_slot);
 }
 
 template <int DT>
@@ -160,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void mb_fwd_kernel(const Args a, double* 
     using F = typename Compute<DT>::type;
     __shared__ int s_slot[kThreads];
     __shared__ F s_cw[kMaxD];
-    const Range r = range_of(a);
+    const Range r = range_of(a.nqb, kThreads, a.Q);
     build_table<DT>(a, r.b, r.q0, r.nq, s_slot, s_cw);
     double l1 = 0.0, iou = 0.0;
     const int j = s_slot[threadIdx.x];   // kNoSlot at and past nq
@@ -210,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_kernel(const Args a, const O*
     using F = typename Compute<DT>::type;
     __shared__ int s_slot[kThreads];
     __shared__ F s_cw[kMaxD];
-    const Range r = range_of(a);
+    const Range r = range_of(a.nqb, kThreads, a.Q);
     build_table<DT>(a, r.b, r.q0, r.nq, s_slot, s_cw);
     const double dn = *denom;
     const F s1 = grad_l1 ? (F)((double)grad_l1[r.b] / dn) : F(0), s2 = grad_iou ? (F)((double)grad_iou[r.b] / dn) : F(0);
@@ -250,12 +221,7 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_kernel(const Args a, const O*
 // the table of a whole frame: tab[q] = slot or kNoSlot
 void host_table(const Args& a, long long b, std::vector<int>& tab)
 {
-    tab.assign((size_t)a.Q, kNoSlot);
-    const long long n = clamp_count(a.counts, b, a.K, 1);
-    for (long long j = 0; j < n; ++j) {
-        const long long q = load_index(a.pind, b * a.K + j, a.idx64), g = load_index(a.gind, b * a.K + j, a.idx64);
-        if (q >= 0 && q < a.Q && g >= 0 && g < a.G && tab[(size_t)q] == kNoSlot) tab[(size_t)q] = (int)j;
-    }
+    host_pair_table(a.pind, a.gind, a.idx64, a.counts, b, a.K, a.Q, a.G, tab);
 }
 
 template <int DT>
@@ -263,10 +229,7 @@ void host_fwd(const Args& a, const accv_matched_box_params* p, void* out_v, doub
 {
     using F = typename Compute<DT>::type;
     F* out = static_cast<F*>(out_v);
-    unsigned long long m = 0;
-    if (p->avg_mode == ACCV_FL_AVG_NUM_POS)
-        for (long long b = 0; b < a.B; ++b) m += (unsigned long long)clamp_count(a.counts, b, a.K, 1);
-    const double denom = denominator(p->avg_mode, p->avg_factor, p->avg_factor_dev, m);
+    const double denom = host_denom(a.counts, a.B, a.K, p->avg_mode, p->avg_factor, p->avg_factor_dev);
     F cw[kMaxD];
     for (int d = 0; d < kMaxD; ++d) cw[d] = d < a.D ? code_weight<DT>(a, d) : F(0);
     std::vector<int> tab;
@@ -326,15 +289,10 @@ int check_args(const char* who, const void* pred, const void* gt, const void* pi
                long long sq, const accv_matched_box_params* p, bool forward, Args& a, int* empty)
 {
     *empty = 0;
-    if (!p) return accv::fail(ACCV_EINVAL, "%s: null params", who);
-    if (B < 0 || Q < 0 || D < 0 || G < 0 || K < 0) return accv::fail(ACCV_EINVAL, "%s: negative size", who);
-    if (dtype < kF32 || dtype > kF64) return accv::fail(ACCV_EINVAL, "%s: unknown dtype code %d", who, dtype);
-    if (flags & ~kKnownFlags) return accv::fail(ACCV_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (int rc = check_pair_sizes(who, p, {B, Q, D, G, K}, dtype, flags, kKnownFlags)) return rc;
     if (p->iou_kind < ACCV_MB_IOU_NONE || p->iou_kind > ACCV_MB_GIOU)
         return accv::fail(ACCV_EINVAL, "%s: unknown IoU kind %d", who, p->iou_kind);
-    if (forward && (p->avg_mode < ACCV_FL_AVG_NUM_POS || p->avg_mode > ACCV_FL_AVG_DEVICE))
-        return accv::fail(ACCV_EINVAL, "%s: unknown avg_factor mode %d", who, p->avg_mode);
-    if (K > INT_MAX) return accv::fail(ACCV_EINVAL, "%s: K is limited to 2^31 - 1", who);
+    if (int rc = check_pair_mode(who, forward, p->avg_mode, K, 0, "K is")) return rc;
     if (B == 0 || Q == 0) {
         *empty = 1;
         return ACCV_OK;
@@ -342,13 +300,10 @@ int check_args(const char* who, const void* pred, const void* gt, const void* pi
     if (D < 1 || D > kMaxD) return accv::fail(ACCV_EINVAL, "%s: needs 1 <= D <= %d (got %lld)", who, kMaxD, D);
     if (p->iou_kind != ACCV_MB_IOU_NONE && D != 4) return accv::fail(ACCV_EINVAL, "%s: an IoU kind needs D == 4 (got %lld)", who, D);
     if (sq < D || sb < 0) return accv::fail(ACCV_EINVAL, "%s: query stride %lld below D = %lld, or negative batch stride", who, sq, D);
-    if (!pred || !counts) return accv::fail(ACCV_EINVAL, "%s: null boxes / counts pointer", who);
-    if (K > 0 && (!pind || !gind)) return accv::fail(ACCV_EINVAL, "%s: null index pointer", who);
+    if (int rc = check_pair_pointers(who, pred != nullptr, "boxes / counts", counts, pind, gind, K)) return rc;
     if (K > 0 && G > 0 && !gt) return accv::fail(ACCV_EINVAL, "%s: null ground-truth pointer", who);
     if (reinterpret_cast<uintptr_t>(pred) % (uintptr_t)elem_size(dtype) || reinterpret_cast<uintptr_t>(gt) % (uintptr_t)elem_size(dtype))
         return accv::fail(ACCV_EINVAL, "%s: boxes are not aligned to their element size", who);
-    if (forward && p->avg_mode == ACCV_FL_AVG_DEVICE && !p->avg_factor_dev)
-        return accv::fail(ACCV_EINVAL, "%s: null avg_factor pointer", who);
     a.p = pred, a.g = gt, a.pind = pind, a.gind = gind, a.counts = counts;
     a.w = p->query_weights, a.cw_dev = p->code_weights_dev;
     for (int d = 0; d < kMaxD; ++d) a.cw[d] = p->code_weights[d];
@@ -356,7 +311,7 @@ int check_args(const char* who, const void* pred, const void* gt, const void* pi
     a.B = B, a.Q = Q, a.D = D, a.G = G, a.K = K, a.sb = sb, a.sq = sq;
     a.nqb = (Q + kThreads - 1) / kThreads;
     a.idx64 = (flags & ACCV_MB_IDX_I64) ? 1 : 0, a.cxcywh = (flags & ACCV_MB_CXCYWH) ? 1 : 0, a.kind = p->iou_kind;
-    if (a.nqb > accv::kGridLimit / B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld workgroups exceed the grid limit", who, B, a.nqb);
+    if (int rc = check_pair_launch(who, forward, p->avg_mode, p->avg_factor_dev, B, a.nqb)) return rc;
     if (Q > LLONG_MAX / D / B) return accv::fail(ACCV_EINVAL, "%s: B x Q x D overflows", who);
     return ACCV_OK;
 }
@@ -366,7 +321,7 @@ void launch_fwd(const Args& a, const accv_matched_box_params* p, double* part, v
 {
     using O = typename Compute<DT>::type;
     hipLaunchKernelGGL(mb_fwd_kernel<DT>, dim3((unsigned)(a.B * a.nqb)), dim3(kThreads), 0, s, a, part);
-    hipLaunchKernelGGL(pair_finish_kernel<O>, dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
+    hipLaunchKernelGGL((pair_finish_kernel<2, O>), dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
                        p->avg_factor, p->avg_factor_dev, static_cast<O*>(out), out_denom);
 }
 
@@ -407,12 +362,7 @@ int accv_matched_box_loss(const void* pred_boxes, const void* gt_boxes, const vo
     if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
-    switch (dtype) {
-        case kF32: launch_fwd<kF32>(a, params, part, out, out_denom, s); break;
-        case kF16: launch_fwd<kF16>(a, params, part, out, out_denom, s); break;
-        case kBF16: launch_fwd<kBF16>(a, params, part, out, out_denom, s); break;
-        default: launch_fwd<kF64>(a, params, part, out, out_denom, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { launch_fwd<dt()>(a, params, part, out, out_denom, s); });
     return accv::check_launch(who);
 }
 
@@ -432,12 +382,7 @@ int accv_matched_box_loss_bwd(const void* pred_boxes, const void* gt_boxes, cons
     if (reinterpret_cast<uintptr_t>(grad_boxes) % (uintptr_t)elem_size(dtype))
         return accv::fail(ACCV_EINVAL, "%s: the gradient is not aligned to its element size", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case kF32: launch_bwd<kF32>(a, grad_l1, grad_iou, denom, grad_boxes, s); break;
-        case kF16: launch_bwd<kF16>(a, grad_l1, grad_iou, denom, grad_boxes, s); break;
-        case kBF16: launch_bwd<kBF16>(a, grad_l1, grad_iou, denom, grad_boxes, s); break;
-        default: launch_bwd<kF64>(a, grad_l1, grad_iou, denom, grad_boxes, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { launch_bwd<dt()>(a, grad_l1, grad_iou, denom, grad_boxes, s); });
     return accv::check_launch(who);
 }
 
@@ -454,17 +399,7 @@ int accv_matched_box_loss_host(const void* pred_boxes, const void* gt_boxes, con
         return rc;
     if (empty) return ACCV_OK;
     if (!out || !out_denom) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
-    try {
-        switch (dtype) {
-            case kF32: host_fwd<kF32>(a, params, out, out_denom); break;
-            case kF16: host_fwd<kF16>(a, params, out, out_denom); break;
-            case kBF16: host_fwd<kBF16>(a, params, out, out_denom); break;
-            default: host_fwd<kF64>(a, params, out, out_denom); break;
-        }
-    } catch (const std::bad_alloc&) {
-        return accv::fail(ACCV_ERUNTIME, "%s: out of host memory", who);
-    }
-    return ACCV_OK;
+    return dispatch_host(who, dtype, [&](auto dt) { host_fwd<dt()>(a, params, out, out_denom); });
 }
 
 int accv_matched_box_loss_bwd_host(const void* pred_boxes, const void* gt_boxes, const void* pred_ind, const void* gt_ind,
@@ -481,17 +416,7 @@ int accv_matched_box_loss_bwd_host(const void* pred_boxes, const void* gt_boxes,
         return rc;
     if (empty) return ACCV_OK;
     if (!denom || !grad_boxes) return accv::fail(ACCV_EINVAL, "%s: null denom / gradient pointer", who);
-    try {
-        switch (dtype) {
-            case kF32: host_bwd<kF32>(a, grad_l1, grad_iou, denom, grad_boxes); break;
-            case kF16: host_bwd<kF16>(a, grad_l1, grad_iou, denom, grad_boxes); break;
-            case kBF16: host_bwd<kBF16>(a, grad_l1, grad_iou, denom, grad_boxes); break;
-            default: host_bwd<kF64>(a, grad_l1, grad_iou, denom, grad_boxes); break;
-        }
-    } catch (const std::bad_alloc&) {
-        return accv::fail(ACCV_ERUNTIME, "%s: out of host memory", who);
-    }
-    return ACCV_OK;
+    return dispatch_host(who, dtype, [&](auto dt) { host_bwd<dt()>(a, grad_l1, grad_iou, denom, grad_boxes); });
 }
 
 }  // extern "C"

@@ -8,12 +8,13 @@
 // The [B, Q, C] one-hot target of the torch composition is never built.  Per-element arithmetic: matched_focal_arith.h.
 //
 // Forward: a workgroup owns a range of queries of one frame.  It builds the range's query -> label table in LDS
-// (atomicMin on the slot number in LDS, then the label look-up of the winning slot; no global atomics), then streams the
+// (the pair rule of matched_pairs.h, then the label look-up of the winning slot; no global atomics), then streams the
 // range's logits — one 16-byte load per lane and step where the rows of the range are contiguous (element loads up to the
 // first 16-byte boundary and after the last one), element loads for strided queries — and accumulates in a double per
 // lane.  A lane finds (query, class) of its first vector with ONE 32-bit division and walks on by additions.  Wave
-// shuffle + LDS give one partial per workgroup in the caller's workspace; a one-block launch adds each frame's partials
-// in a fixed order, counts the pairs, applies the denominator and leaves it on the device for the backward.
+// shuffle + LDS give one partial per workgroup in the caller's workspace; the one-block launch of matched_pairs.h adds
+// each frame's partials in a fixed order, counts the pairs, applies the denominator and leaves it on the device for the
+// backward.
 // Backward: the same table, then every element of the contiguous [B, Q, C] gradient written exactly once in the logits
 // dtype: no zero fill, no atomics.  Neither direction synchronises; both are bitwise reproducible.
 // Bandwidth / launch bound work: no MFMA.
@@ -21,11 +22,11 @@
 
 #include <climits>
 #include <cstdint>
-#include <new>
 #include <vector>
 
 #include "accv_common.h"
 #include "matched_focal_arith.h"
+#include "matched_pairs.h"
 
 #pragma clang fp contract(off)
 
@@ -34,11 +35,9 @@ namespace {
 using namespace accv_mf;
 
 constexpr int kThreads = 256;
-constexpr int kFinishThreads = 1024;
 constexpr int kMaxQ = 1024;                 // queries per workgroup the LDS tables hold
 constexpr long long kTargetElems = 8192;    // elements per workgroup aimed at
 constexpr unsigned kKnownFlags = ACCV_MF_IDX_I64 | ACCV_MF_LABELS_I64;
-constexpr int kNoSlot = INT_MAX;
 
 struct Args {
     const void* x;              // [B, Q, C] logits, element (b, q, c) at b * sb + q * sq + c
@@ -80,19 +79,7 @@ __device__ __forceinline__ void build_table(const Args& a, long long b, long lon
     const int tid = threadIdx.x;
     for (int i = tid; i < nq; i += kThreads) s_lab[i] = kNoSlot;
     __syncthreads();
-    const long long n = clamp_count(a.counts, b, a.K, 1);
-    for (long long j = tid; j < n; j += kThreads) {
-        long long q, g;   // both indices in ONE branch on their dtype, so the two loads are in flight together
-        if (a.idx64) {
-            q = static_cast<const long long*>(a.pind)[b * a.K + j];
-            g = static_cast<const long long*>(a.gind)[b * a.K + j];
-        } else {
-            q = static_cast<const int*>(a.pind)[b * a.K + j];
-            g = static_cast<const int*>(a.gind)[b * a.K + j];
-        }
-        if (q >= q0 && q < q0 + nq && g >= 0 && g < a.G) atomicMin(&s_lab[(int)(q - q0)], (int)j);
-    }
-    __syncthreads();
+    scan_pairs<kThreads>(a.pind, a.gind, a.idx64, a.counts, b, a.K, a.G, q0, nq, s_lab);
     for (int i = tid; i < nq; i += kThreads) {
         const int j = s_lab[i];
         s_lab[i] = j == kNoSlot ? -1 : label_of_slot(a, b, j);
@@ -118,22 +105,6 @@ __device__ __forceinline__ void walk(unsigned e0, unsigned n, unsigned C, Fn&& f
     }
 }
 
-// the range of a workgroup: frame, first query, number of queries, elements
-struct Range {
-    long long b, q0;
-    int nq;
-    unsigned total;
-};
-__device__ __forceinline__ Range range_of(const Args& a)
-{
-    Range r;
-    r.b = blockIdx.x / a.nqb;
-    r.q0 = (blockIdx.x - r.b * a.nqb) * a.qpb;
-    const long long left = a.Q - r.q0;
-    r.nq = (int)(left < a.qpb ? left : a.qpb);
-    r.total = (unsigned)r.nq * (unsigned)a.C;
-    return r;
-}
 // elements before the first 16-byte boundary of a range that starts at address `addr`
 template <int DT>
 __device__ __forceinline__ unsigned head_of(uintptr_t addr, unsigned total)
@@ -150,7 +121,8 @@ __global__ __launch_bounds__(kThreads) void mf_fwd_kernel(const Args a, const Co
     constexpr int V = 16 / elem_size(DT);   // elements of a 16-byte access
     __shared__ int s_lab[kMaxQ];
     __shared__ F s_w[kMaxQ];
-    const Range r = range_of(a);
+    const Range r = range_of(a.nqb, a.qpb, a.Q);
+    const unsigned total = (unsigned)r.nq * (unsigned)a.C;   // elements of the range
     build_table<DT>(a, r.b, r.q0, r.nq, s_lab, s_w);
     const unsigned C = (unsigned)a.C;
     const long long first = r.b * a.sb + r.q0 * a.sq;   // element offset of the range's first logit
@@ -158,8 +130,8 @@ __global__ __launch_bounds__(kThreads) void mf_fwd_kernel(const Args a, const Co
     auto one = [&](F x, unsigned q, unsigned c) { acc += (double)(s_w[q] * focal_value<F, G2>(x, (int)c == s_lab[q], k)); };
     if (a.sq == a.C) {
         const char* base = static_cast<const char*>(a.x) + first * elem_size(DT);
-        const unsigned head = head_of<DT>(reinterpret_cast<uintptr_t>(base), r.total);
-        const unsigned nvec = (r.total - head) / V, tail0 = head + nvec * V;
+        const unsigned head = head_of<DT>(reinterpret_cast<uintptr_t>(base), total);
+        const unsigned nvec = (total - head) / V, tail0 = head + nvec * V;
         walk<V>(head, nvec, C, [&](unsigned i, unsigned q, unsigned c) {
             const uint4 v = *reinterpret_cast<const uint4*>(base + ((size_t)head + (size_t)i * V) * elem_size(DT));
             F x[V];
@@ -173,50 +145,12 @@ __global__ __launch_bounds__(kThreads) void mf_fwd_kernel(const Args a, const Co
         // at most V - 1 elements on either side of the vectors
         const unsigned t = threadIdx.x;
         if (t < head) one(load<DT>(a.x, first + t), t / C, t % C);
-        if (t < r.total - tail0) one(load<DT>(a.x, first + tail0 + t), (tail0 + t) / C, (tail0 + t) % C);
+        if (t < total - tail0) one(load<DT>(a.x, first + tail0 + t), (tail0 + t) / C, (tail0 + t) % C);
     } else {
-        walk<1>(0u, r.total, C, [&](unsigned, unsigned q, unsigned c) { one(load<DT>(a.x, first + (long long)q * a.sq + c), q, c); });
+        walk<1>(0u, total, C, [&](unsigned, unsigned q, unsigned c) { one(load<DT>(a.x, first + (long long)q * a.sq + c), q, c); });
     }
     acc = block_sum<double, kThreads>(acc);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// one workgroup, a wave per frame: the frame's partials in a fixed order, the number of pairs, the denominator.
-// Not block_sum: 1024 threads whose 16 wave counts are added one after the other (integers, any order gives the same
-// count), and per-frame sums that stay inside one wave.  Both butterflies keep their own order.
-template <class O>
-__global__ __launch_bounds__(kFinishThreads) void mf_finish_kernel(const double* __restrict__ part,
-                                                                   const long long* __restrict__ counts, long long B,
-                                                                   long long nqb, long long K, int avg_mode, double avg_value,
-                                                                   const float* __restrict__ avg_dev, O* __restrict__ out,
-                                                                   double* __restrict__ out_denom)
-{
-    __shared__ unsigned long long s_cnt[kFinishThreads / 64];
-    __shared__ double s_denom;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long m = 0;
-    if (avg_mode == ACCV_FL_AVG_NUM_POS)
-        for (long long b = threadIdx.x; b < B; b += kFinishThreads) m += (unsigned long long)clamp_count(counts, b, K, 1);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m += __shfl_xor(m, s);
-    if (lane == 0) s_cnt[wave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long total = 0;
-        for (int i = 0; i < kFinishThreads / 64; ++i) total += s_cnt[i];
-        const double denom = denominator(avg_mode, avg_value, avg_dev, total);
-        s_denom = denom;
-        *out_denom = denom;
-    }
-    __syncthreads();
-    const double denom = s_denom;
-    for (long long b = wave; b < B; b += kFinishThreads / 64) {
-        double acc = 0.0;
-        for (long long i = lane; i < nqb; i += 64) acc += part[b * nqb + i];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-        if (lane == 0) out[b] = (O)(acc / denom);
-    }
 }
 
 template <int DT, bool G2, class O>
@@ -228,7 +162,8 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
     constexpr int V = 16 / elem_size(DT);   // elements of a 16-byte access
     __shared__ int s_lab[kMaxQ];
     __shared__ F s_w[kMaxQ];
-    const Range r = range_of(a);
+    const Range r = range_of(a.nqb, a.qpb, a.Q);
+    const unsigned total = (unsigned)r.nq * (unsigned)a.C;   // elements of the range
     build_table<DT>(a, r.b, r.q0, r.nq, s_lab, s_w);
     const unsigned C = (unsigned)a.C;
     const long long first = r.b * a.sb + r.q0 * a.sq;
@@ -239,8 +174,8 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
     char* gbase = static_cast<char*>(grad) + gfirst * elem_size(DT);
     const bool same = ((reinterpret_cast<uintptr_t>(base) ^ reinterpret_cast<uintptr_t>(gbase)) & 15u) == 0;
     if (a.sq == a.C && same) {
-        const unsigned head = head_of<DT>(reinterpret_cast<uintptr_t>(base), r.total);
-        const unsigned nvec = (r.total - head) / V, tail0 = head + nvec * V;
+        const unsigned head = head_of<DT>(reinterpret_cast<uintptr_t>(base), total);
+        const unsigned nvec = (total - head) / V, tail0 = head + nvec * V;
         walk<V>(head, nvec, C, [&](unsigned i, unsigned q, unsigned c) {
             const size_t at = ((size_t)head + (size_t)i * V) * elem_size(DT);
             const uint4 v = *reinterpret_cast<const uint4*>(base + at);
@@ -255,10 +190,10 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
         });
         const unsigned t = threadIdx.x;
         if (t < head) store<DT>(grad, gfirst + t, one(load<DT>(a.x, first + t), t / C, t % C));
-        if (t < r.total - tail0)
+        if (t < total - tail0)
             store<DT>(grad, gfirst + tail0 + t, one(load<DT>(a.x, first + tail0 + t), (tail0 + t) / C, (tail0 + t) % C));
     } else {
-        walk<1>(0u, r.total, C, [&](unsigned i, unsigned q, unsigned c) {
+        walk<1>(0u, total, C, [&](unsigned i, unsigned q, unsigned c) {
             store<DT>(grad, gfirst + i, one(load<DT>(a.x, first + (long long)q * a.sq + c), q, c));
         });
     }
@@ -268,21 +203,8 @@ __global__ __launch_bounds__(kThreads) void mf_bwd_kernel(const Args a, const Co
 // the table of a whole frame: tab[q] = class or -1
 void host_table(const Args& a, long long b, std::vector<int>& tab)
 {
-    tab.assign((size_t)a.Q, kNoSlot);
-    const long long n = clamp_count(a.counts, b, a.K, 1);
-    for (long long j = 0; j < n; ++j) {
-        const long long q = load_index(a.pind, b * a.K + j, a.idx64), g = load_index(a.gind, b * a.K + j, a.idx64);
-        if (q >= 0 && q < a.Q && g >= 0 && g < a.G && tab[(size_t)q] == kNoSlot) tab[(size_t)q] = (int)j;
-    }
-    for (long long q = 0; q < a.Q; ++q) tab[(size_t)q] = tab[(size_t)q] == kNoSlot ? -1 : label_of_slot(a, b, tab[(size_t)q]);
-}
-
-double host_denom(const Args& a, int avg_mode, double avg_value, const float* avg_ptr)
-{
-    unsigned long long m = 0;
-    if (avg_mode == ACCV_FL_AVG_NUM_POS)
-        for (long long b = 0; b < a.B; ++b) m += (unsigned long long)clamp_count(a.counts, b, a.K, 1);
-    return denominator(avg_mode, avg_value, avg_ptr, m);
+    host_pair_table(a.pind, a.gind, a.idx64, a.counts, b, a.K, a.Q, a.G, tab);
+    for (int& t : tab) t = t == kNoSlot ? -1 : label_of_slot(a, b, t);
 }
 
 template <int DT, bool G2, class O>
@@ -290,7 +212,7 @@ void host_fwd(const Args& a, const accv_matched_focal_params* p, O* out, double*
 {
     using F = typename Compute<DT>::type;
     const Coef<F> k = make_coef<F>(p->alpha, p->gamma);
-    const double denom = host_denom(a, p->avg_mode, p->avg_factor, p->avg_factor_dev);
+    const double denom = host_denom(a.counts, a.B, a.K, p->avg_mode, p->avg_factor, p->avg_factor_dev);
     std::vector<int> tab;
     for (long long b = 0; b < a.B; ++b) {
         host_table(a, b, tab);
@@ -332,32 +254,23 @@ int check_args(const char* who, const void* logits, const void* labels, const vo
                long long K, long long sb, long long sq, const accv_matched_focal_params* p, bool forward, Args& a, int* empty)
 {
     *empty = 0;
-    if (!p) return accv::fail(ACCV_EINVAL, "%s: null params", who);
-    if (B < 0 || Q < 0 || C < 0 || G < 0 || K < 0) return accv::fail(ACCV_EINVAL, "%s: negative size", who);
-    if (dtype < kF32 || dtype > kF64) return accv::fail(ACCV_EINVAL, "%s: unknown dtype code %d", who, dtype);
-    if (flags & ~kKnownFlags) return accv::fail(ACCV_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (int rc = check_pair_sizes(who, p, {B, Q, C, G, K}, dtype, flags, kKnownFlags)) return rc;
     if (!(p->gamma >= 0.0)) return accv::fail(ACCV_EINVAL, "%s: needs gamma >= 0 (got %g)", who, p->gamma);
     if (p->alpha != p->alpha) return accv::fail(ACCV_EINVAL, "%s: alpha is NaN", who);
-    if (forward && (p->avg_mode < ACCV_FL_AVG_NUM_POS || p->avg_mode > ACCV_FL_AVG_DEVICE))
-        return accv::fail(ACCV_EINVAL, "%s: unknown avg_factor mode %d", who, p->avg_mode);
-    if (C > INT_MAX || K > INT_MAX) return accv::fail(ACCV_EINVAL, "%s: C and K are limited to 2^31 - 1", who);
+    if (int rc = check_pair_mode(who, forward, p->avg_mode, K, C, "C and K are")) return rc;
     if (B == 0 || Q == 0 || C == 0) {
         *empty = 1;
         return ACCV_OK;
     }
     if (sq < C || sb < 0) return accv::fail(ACCV_EINVAL, "%s: query stride %lld below C = %lld, or negative batch stride", who, sq, C);
-    if (!logits || !counts) return accv::fail(ACCV_EINVAL, "%s: null logits / counts pointer", who);
-    if (K > 0 && (!pind || !gind)) return accv::fail(ACCV_EINVAL, "%s: null index pointer", who);
+    if (int rc = check_pair_pointers(who, logits != nullptr, "logits / counts", counts, pind, gind, K)) return rc;
     if (K > 0 && G > 0 && !labels) return accv::fail(ACCV_EINVAL, "%s: null labels pointer", who);
     if (reinterpret_cast<uintptr_t>(logits) % (uintptr_t)elem_size(dtype)) return accv::fail(ACCV_EINVAL, "%s: logits are not aligned to their element size", who);
-    if (forward && p->avg_mode == ACCV_FL_AVG_DEVICE && !p->avg_factor_dev)
-        return accv::fail(ACCV_EINVAL, "%s: null avg_factor pointer", who);
     a.x = logits, a.labels = labels, a.pind = pind, a.gind = gind, a.counts = counts, a.w = nullptr;
     a.B = B, a.Q = Q, a.C = C, a.G = G, a.K = K, a.sb = sb, a.sq = sq;
     a.idx64 = (flags & ACCV_MF_IDX_I64) ? 1 : 0, a.lab64 = (flags & ACCV_MF_LABELS_I64) ? 1 : 0;
     geometry(Q, C, a.qpb, a.nqb);
-    if (a.nqb > accv::kGridLimit / B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld workgroups exceed the grid limit", who, B, a.nqb);
-    return ACCV_OK;
+    return check_pair_launch(who, forward, p->avg_mode, p->avg_factor_dev, B, a.nqb);
 }
 
 template <int DT>
@@ -369,7 +282,7 @@ void launch_fwd(const Args& a, const accv_matched_focal_params* p, double* part,
     const dim3 grid((unsigned)(a.B * a.nqb)), block(kThreads);
     if (p->gamma == 2.0) hipLaunchKernelGGL((mf_fwd_kernel<DT, true>), grid, block, 0, s, a, k, part);
     else hipLaunchKernelGGL((mf_fwd_kernel<DT, false>), grid, block, 0, s, a, k, part);
-    hipLaunchKernelGGL(mf_finish_kernel<O>, dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
+    hipLaunchKernelGGL((pair_finish_kernel<1, O>), dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
                        p->avg_factor, p->avg_factor_dev, static_cast<O*>(out), out_denom);
 }
 
@@ -434,12 +347,7 @@ int accv_matched_focal_loss(const void* logits, const void* gt_labels, const voi
     if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
-    switch (dtype) {
-        case kF32: launch_fwd<kF32>(a, params, part, out, out_denom, s); break;
-        case kF16: launch_fwd<kF16>(a, params, part, out, out_denom, s); break;
-        case kBF16: launch_fwd<kBF16>(a, params, part, out, out_denom, s); break;
-        default: launch_fwd<kF64>(a, params, part, out, out_denom, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { launch_fwd<dt()>(a, params, part, out, out_denom, s); });
     return accv::check_launch(who);
 }
 
@@ -461,12 +369,7 @@ int accv_matched_focal_loss_bwd(const void* logits, const void* gt_labels, const
     if (reinterpret_cast<uintptr_t>(grad_logits) % (uintptr_t)elem_size(dtype))
         return accv::fail(ACCV_EINVAL, "%s: the gradient is not aligned to its element size", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case kF32: launch_bwd<kF32>(a, params, grad_out, denom, grad_logits, s); break;
-        case kF16: launch_bwd<kF16>(a, params, grad_out, denom, grad_logits, s); break;
-        case kBF16: launch_bwd<kBF16>(a, params, grad_out, denom, grad_logits, s); break;
-        default: launch_bwd<kF64>(a, params, grad_out, denom, grad_logits, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { launch_bwd<dt()>(a, params, grad_out, denom, grad_logits, s); });
     return accv::check_launch(who);
 }
 
@@ -484,17 +387,7 @@ int accv_matched_focal_loss_host(const void* logits, const void* gt_labels, cons
     if (empty) return ACCV_OK;
     a.w = query_weights_or_null;
     if (!out || !out_denom) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
-    try {
-        switch (dtype) {
-            case kF32: run_host_fwd<kF32>(a, params, out, out_denom); break;
-            case kF16: run_host_fwd<kF16>(a, params, out, out_denom); break;
-            case kBF16: run_host_fwd<kBF16>(a, params, out, out_denom); break;
-            default: run_host_fwd<kF64>(a, params, out, out_denom); break;
-        }
-    } catch (const std::bad_alloc&) {
-        return accv::fail(ACCV_ERUNTIME, "%s: out of host memory", who);
-    }
-    return ACCV_OK;
+    return dispatch_host(who, dtype, [&](auto dt) { run_host_fwd<dt()>(a, params, out, out_denom); });
 }
 
 int accv_matched_focal_loss_bwd_host(const void* logits, const void* gt_labels, const void* pred_ind, const void* gt_ind,
@@ -512,17 +405,7 @@ int accv_matched_focal_loss_bwd_host(const void* logits, const void* gt_labels, 
     if (empty) return ACCV_OK;
     a.w = query_weights_or_null;
     if (!grad_out || !denom || !grad_logits) return accv::fail(ACCV_EINVAL, "%s: null grad_out / denom / gradient pointer", who);
-    try {
-        switch (dtype) {
-            case kF32: run_host_bwd<kF32>(a, params, grad_out, denom, grad_logits); break;
-            case kF16: run_host_bwd<kF16>(a, params, grad_out, denom, grad_logits); break;
-            case kBF16: run_host_bwd<kBF16>(a, params, grad_out, denom, grad_logits); break;
-            default: run_host_bwd<kF64>(a, params, grad_out, denom, grad_logits); break;
-        }
-    } catch (const std::bad_alloc&) {
-        return accv::fail(ACCV_ERUNTIME, "%s: out of host memory", who);
-    }
-    return ACCV_OK;
+    return dispatch_host(who, dtype, [&](auto dt) { run_host_bwd<dt()>(a, params, grad_out, denom, grad_logits); });
 }
 
 }  // extern "C"

@@ -11,9 +11,9 @@
 // kQueriesPerWave queries and keeps their sums side by side, so one LDS read of the ground truth serves all of them; the
 // query's point is a broadcast read.  No order is ever written anywhere.  One launch.
 // Loss forward: a workgroup owns kLossQueries consecutive queries of one frame and builds their query -> slot table in LDS
-// (the pair rule of matched_box.hip).  A wave takes one matched pair at a time: its lanes search the orders side by side
+// (the pair rule of matched_pairs.h).  A wave takes one matched pair at a time: its lanes search the orders side by side
 // (lowest v on ties), then take the points of the best order side by side and the wave adds them up in f64 in a fixed
-// order.  One (pts, dir) partial per workgroup; the one-block launch of matched_pair_finish.h adds them per frame.
+// order.  One (pts, dir) partial per workgroup; the one-block launch of matched_pairs.h adds them per frame.
 // Loss backward: the same table and search, then every element of the contiguous [B, Q, P, D] gradient written exactly
 // once, +0 for a query without a pair: no zero fill, no atomics.
 // Neither direction synchronises; both are bitwise reproducible.  No MFMA: the work is absolute differences and minima.
@@ -22,11 +22,10 @@
 #include <climits>
 #include <cstdint>
 #include <limits>
-#include <new>
 #include <vector>
 
 #include "accv_common.h"
-#include "matched_pair_finish.h"
+#include "matched_pairs.h"
 #include "polyline_match_arith.h"
 
 #pragma clang fp contract(off)
@@ -43,7 +42,6 @@ constexpr int kQueryTile = kWaves * kQueriesPerWave;        // queries per workg
 constexpr int kLossQueries = 64;                            // queries per workgroup of the loss kernels
 constexpr size_t kLdsBudget = 64 * 1024;                    // dynamic LDS of the cost kernel
 constexpr unsigned kKnownFlags = ACCV_PM_IDX_I64 | ACCV_PM_REVERSIBLE | ACCV_PM_LABELS_I64 | ACCV_PM_CLOSED_I32 | ACCV_PM_CLOSED_I64;
-constexpr int kNoSlot = INT_MAX;
 
 struct Args {
     const void* x;              // [B, Q, P, D] predictions, element (b, q, i) at b * sb + q * sq + i
@@ -198,39 +196,13 @@ void cost_host(const Args& a, const Params<typename Compute<DT>::type>& p)
 }
 
 // ---------------------------------------------------------------------------------------------------------- loss, device
-// s_slot[i] = the slot of the pair of query q0 + i, or kNoSlot (build_table of matched_box.hip for kLossQueries queries)
+// s_slot[i] = the slot of the pair of query q0 + i, or kNoSlot
 __device__ __forceinline__ void build_table(const Args& a, long long b, long long q0, int nq, int* s_slot)
 {
     const int tid = threadIdx.x;
     if (tid < kLossQueries) s_slot[tid] = kNoSlot;
     __syncthreads();
-    const long long n = clamp_count(a.counts, b, a.K, 1);
-    for (long long j = tid; j < n; j += kThreads) {
-        long long q, g;
-        if (a.idx64) {
-            q = static_cast<const long long*>(a.pind)[b * a.K + j];
-            g = static_cast<const long long*>(a.gind)[b * a.K + j];
-        } else {
-            q = static_cast<const int*>(a.pind)[b * a.K + j];
-            g = static_cast<const int*>(a.gind)[b * a.K + j];
-        }
-        if (q >= q0 && q < q0 + nq && g >= 0 && g < a.G) atomicMin(&s_slot[(int)(q - q0)], (int)j);
-    }
-    __syncthreads();
-}
-
-struct Range {
-    long long b, q0;
-    int nq;
-};
-__device__ __forceinline__ Range range_of(const Args& a)
-{
-    Range r;
-    r.b = blockIdx.x / a.nqb;
-    r.q0 = (blockIdx.x - r.b * a.nqb) * kLossQueries;
-    const long long left = a.Q - r.q0;
-    r.nq = (int)(left < kLossQueries ? left : kLossQueries);
-    return r;
+    scan_pairs<kThreads>(a.pind, a.gind, a.idx64, a.counts, b, a.K, a.G, q0, nq, s_slot);
 }
 
 // best_variant by a whole wave: lane l takes the orders l, l + 64, ...; the same v in every lane
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(kThreads) void pm_fwd_kernel(const Args a, double* 
 {
     using F = typename Compute<DT>::type;
     __shared__ int s_slot[kLossQueries];
-    const Range r = range_of(a);
+    const Range r = range_of(a.nqb, kLossQueries, a.Q);
     build_table(a, r.b, r.q0, r.nq, s_slot);
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     double pts = 0.0, dir = 0.0;
@@ -297,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void pm_bwd_kernel(const Args a, const O*
 {
     using F = typename Compute<DT>::type;
     __shared__ int s_slot[kLossQueries];
-    const Range r = range_of(a);
+    const Range r = range_of(a.nqb, kLossQueries, a.Q);
     build_table(a, r.b, r.q0, r.nq, s_slot);
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const double dn = *denom;
@@ -328,12 +300,7 @@ __global__ __launch_bounds__(kThreads) void pm_bwd_kernel(const Args a, const O*
 // ------------------------------------------------------------------------------------------------------------ loss, host
 void host_table(const Args& a, long long b, std::vector<int>& tab)
 {
-    tab.assign((size_t)a.Q, kNoSlot);
-    const long long n = clamp_count(a.counts, b, a.K, 1);
-    for (long long j = 0; j < n; ++j) {
-        const long long q = load_index(a.pind, b * a.K + j, a.idx64), g = load_index(a.gind, b * a.K + j, a.idx64);
-        if (q >= 0 && q < a.Q && g >= 0 && g < a.G && tab[(size_t)q] == kNoSlot) tab[(size_t)q] = (int)j;
-    }
+    host_pair_table(a.pind, a.gind, a.idx64, a.counts, b, a.K, a.Q, a.G, tab);
 }
 
 template <int DT>
@@ -341,10 +308,7 @@ void host_fwd(const Args& a, const accv_polyline_match_params* p, void* out_v, d
 {
     using F = typename Compute<DT>::type;
     F* out = static_cast<F*>(out_v);
-    unsigned long long m = 0;
-    if (p->avg_mode == ACCV_FL_AVG_NUM_POS)
-        for (long long b = 0; b < a.B; ++b) m += (unsigned long long)clamp_count(a.counts, b, a.K, 1);
-    const double denom = denominator(p->avg_mode, p->avg_factor, p->avg_factor_dev, m);
+    const double denom = host_denom(a.counts, a.B, a.K, p->avg_mode, p->avg_factor, p->avg_factor_dev);
     std::vector<int> tab;
     for (long long b = 0; b < a.B; ++b) {
         host_table(a, b, tab);
@@ -413,10 +377,7 @@ int check_common(const char* who, const void* pred, const void* gt, int dtype, u
                  bool need_lines, long long zero_extent, Args& a, int* empty)
 {
     *empty = 0;
-    if (!p) return accv::fail(ACCV_EINVAL, "%s: null params", who);
-    if (B < 0 || Q < 0 || G < 0 || P < 0 || D < 0 || other < 0) return accv::fail(ACCV_EINVAL, "%s: negative size", who);
-    if (dtype < kF32 || dtype > kF64) return accv::fail(ACCV_EINVAL, "%s: unknown dtype code %d", who, dtype);
-    if (flags & ~allowed) return accv::fail(ACCV_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (int rc = check_pair_sizes(who, p, {B, Q, G, P, D, other}, dtype, flags, allowed)) return rc;
     if ((flags & ACCV_PM_CLOSED_I32) && (flags & ACCV_PM_CLOSED_I64))
         return accv::fail(ACCV_EINVAL, "%s: gt_closed cannot be both int32 and int64", who);
     if (zero_extent == 0) {
@@ -469,21 +430,15 @@ int check_loss(const char* who, const void* pred, const void* gt, const void* pi
                int dtype, unsigned flags, long long B, long long Q, long long G, long long P, long long D, long long K,
                const accv_polyline_match_params* p, bool forward, Args& a, int* empty)
 {
-    if (forward && p && (p->avg_mode < ACCV_FL_AVG_NUM_POS || p->avg_mode > ACCV_FL_AVG_DEVICE))
-        return accv::fail(ACCV_EINVAL, "%s: unknown avg_factor mode %d", who, p->avg_mode);
-    if (K > INT_MAX) return accv::fail(ACCV_EINVAL, "%s: K is limited to 2^31 - 1", who);
+    if (int rc = check_pair_mode(who, forward && p, p ? p->avg_mode : 0, K, 0, "K is")) return rc;
     const unsigned allowed = kKnownFlags & ~ACCV_PM_LABELS_I64;
     if (int rc = check_common(who, pred, gt, dtype, flags, allowed, B, Q, G, P, D, K, p, true, B * Q, a, empty)) return rc;
     if (*empty) return ACCV_OK;
-    if (!counts) return accv::fail(ACCV_EINVAL, "%s: null counts pointer", who);
-    if (K > 0 && (!pind || !gind)) return accv::fail(ACCV_EINVAL, "%s: null index pointer", who);
-    if (forward && p->avg_mode == ACCV_FL_AVG_DEVICE && !p->avg_factor_dev)
-        return accv::fail(ACCV_EINVAL, "%s: null avg_factor pointer", who);
+    if (int rc = check_pair_pointers(who, true, "counts", counts, pind, gind, K)) return rc;
     a.counts = counts, a.pind = pind, a.gind = gind, a.K = K;
     a.idx64 = (flags & ACCV_PM_IDX_I64) ? 1 : 0, a.dir = p->dir_loss ? 1 : 0, a.eps = p->dir_eps;
     a.nqb = (Q + kLossQueries - 1) / kLossQueries;
-    if (a.nqb > accv::kGridLimit / B) return accv::fail(ACCV_EINVAL, "%s: %lld x %lld workgroups exceed the grid limit", who, B, a.nqb);
-    return ACCV_OK;
+    return check_pair_launch(who, forward, p->avg_mode, p->avg_factor_dev, B, a.nqb);
 }
 
 template <class F>
@@ -529,7 +484,7 @@ void launch_fwd(const Args& a, const accv_polyline_match_params* p, double* part
 {
     using O = typename Compute<DT>::type;
     hipLaunchKernelGGL(pm_fwd_kernel<DT>, dim3((unsigned)(a.B * a.nqb)), dim3(kThreads), 0, s, a, part);
-    hipLaunchKernelGGL(pair_finish_kernel<O>, dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
+    hipLaunchKernelGGL((pair_finish_kernel<2, O>), dim3(1), dim3(kFinishThreads), 0, s, part, a.counts, a.B, a.nqb, a.K, p->avg_mode,
                        p->avg_factor, p->avg_factor_dev, static_cast<O*>(out), out_denom);
 }
 
@@ -557,12 +512,9 @@ int accv_polyline_matching_cost(const void* pred_lines, const void* gt_lines, co
         return rc;
     if (empty) return ACCV_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case kF32: return launch_cost<kF32>(a, params, s);
-        case kF16: return launch_cost<kF16>(a, params, s);
-        case kBF16: return launch_cost<kBF16>(a, params, s);
-        default: return launch_cost<kF64>(a, params, s);
-    }
+    int rc = ACCV_OK;
+    dispatch_dtype(dtype, [&](auto dt) { rc = launch_cost<dt()>(a, params, s); });
+    return rc;
 }
 
 int accv_polyline_matching_cost_host(const void* pred_lines, const void* gt_lines, const void* scores, const void* gt_labels,
@@ -576,12 +528,7 @@ int accv_polyline_matching_cost_host(const void* pred_lines, const void* gt_line
                             G, P, D, C, scores_stride_b, scores_stride_q, params, out, a, &empty))
         return rc;
     if (empty) return ACCV_OK;
-    switch (dtype) {
-        case kF32: cost_host<kF32>(a, make_params<float>(params)); break;
-        case kF16: cost_host<kF16>(a, make_params<float>(params)); break;
-        case kBF16: cost_host<kBF16>(a, make_params<float>(params)); break;
-        default: cost_host<kF64>(a, make_params<double>(params)); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { cost_host<dt()>(a, make_params<typename Compute<dt()>::type>(params)); });
     return ACCV_OK;
 }
 
@@ -610,12 +557,7 @@ int accv_matched_polyline_loss(const void* pred_lines, const void* gt_lines, con
     if (int rc = accv::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
-    switch (dtype) {
-        case kF32: launch_fwd<kF32>(a, params, part, out, out_denom, s); break;
-        case kF16: launch_fwd<kF16>(a, params, part, out, out_denom, s); break;
-        case kBF16: launch_fwd<kBF16>(a, params, part, out, out_denom, s); break;
-        default: launch_fwd<kF64>(a, params, part, out, out_denom, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { launch_fwd<dt()>(a, params, part, out, out_denom, s); });
     return accv::check_launch(who);
 }
 
@@ -636,12 +578,7 @@ int accv_matched_polyline_loss_bwd(const void* pred_lines, const void* gt_lines,
     if (reinterpret_cast<uintptr_t>(grad_lines) % (uintptr_t)elem_size(dtype))
         return accv::fail(ACCV_EINVAL, "%s: the gradient is not aligned to its element size", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case kF32: launch_bwd<kF32>(a, grad_pts, grad_dir, denom, grad_lines, s); break;
-        case kF16: launch_bwd<kF16>(a, grad_pts, grad_dir, denom, grad_lines, s); break;
-        case kBF16: launch_bwd<kBF16>(a, grad_pts, grad_dir, denom, grad_lines, s); break;
-        default: launch_bwd<kF64>(a, grad_pts, grad_dir, denom, grad_lines, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) { launch_bwd<dt()>(a, grad_pts, grad_dir, denom, grad_lines, s); });
     return accv::check_launch(who);
 }
 
@@ -658,17 +595,7 @@ int accv_matched_polyline_loss_host(const void* pred_lines, const void* gt_lines
         return rc;
     if (empty) return ACCV_OK;
     if (!out || !out_denom) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
-    try {
-        switch (dtype) {
-            case kF32: host_fwd<kF32>(a, params, out, out_denom); break;
-            case kF16: host_fwd<kF16>(a, params, out, out_denom); break;
-            case kBF16: host_fwd<kBF16>(a, params, out, out_denom); break;
-            default: host_fwd<kF64>(a, params, out, out_denom); break;
-        }
-    } catch (const std::bad_alloc&) {
-        return accv::fail(ACCV_ERUNTIME, "%s: out of host memory", who);
-    }
-    return ACCV_OK;
+    return dispatch_host(who, dtype, [&](auto dt) { host_fwd<dt()>(a, params, out, out_denom); });
 }
 
 int accv_matched_polyline_loss_bwd_host(const void* pred_lines, const void* gt_lines, const void* pred_ind,
@@ -685,17 +612,7 @@ int accv_matched_polyline_loss_bwd_host(const void* pred_lines, const void* gt_l
         return rc;
     if (empty) return ACCV_OK;
     if (!denom || !grad_lines) return accv::fail(ACCV_EINVAL, "%s: null denom / gradient pointer", who);
-    try {
-        switch (dtype) {
-            case kF32: host_bwd<kF32>(a, grad_pts, grad_dir, denom, grad_lines); break;
-            case kF16: host_bwd<kF16>(a, grad_pts, grad_dir, denom, grad_lines); break;
-            case kBF16: host_bwd<kBF16>(a, grad_pts, grad_dir, denom, grad_lines); break;
-            default: host_bwd<kF64>(a, grad_pts, grad_dir, denom, grad_lines); break;
-        }
-    } catch (const std::bad_alloc&) {
-        return accv::fail(ACCV_ERUNTIME, "%s: out of host memory", who);
-    }
-    return ACCV_OK;
+    return dispatch_host(who, dtype, [&](auto dt) { host_bwd<dt()>(a, grad_pts, grad_dir, denom, grad_lines); });
 }
 
 }  // extern "C"

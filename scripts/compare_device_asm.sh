@@ -1,23 +1,25 @@
 #!/bin/bash
-# Is the DEVICE code of accv-lab_amd/csrc/draw_heatmap.hip the same as at an earlier commit (default HEAD)?  Compiles the file
+# Is the DEVICE code of a file of accv-lab_amd/csrc (default draw_heatmap.hip) the same as at an earlier commit (default HEAD)?  Compiles the file
 # of that commit (exported into build/asm_cmp/prev, like build_prev_lib.sh) and of the working tree to gfx950 assembly with
 # the Makefile's flags and diffs the two, less the lines that carry the per-compilation __hip_cuid_<hash> symbol (the only
 # lines in which two compilations of one source differ).  An empty diff = all kernels, their metadata and their order are
 # byte-identical: a source-only refactor has the speed of its parent.  Exit status 1 when the assembly differs.
-#   scripts/compare_device_asm.sh [REV] [-DFOO ...]      extra switches go to both compilations (-DACCV_SPLAT_STAMPS)
+#   scripts/compare_device_asm.sh [REV] [FILE.hip] [-DFOO ...]      extra switches go to both compilations (-DACCV_SPLAT_STAMPS)
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 REV="HEAD"
-if [ $# -gt 0 ] && [ "${1#-}" = "$1" ]; then REV="$1"; shift; fi
+SRC="draw_heatmap.hip"
+if [ $# -gt 0 ] && [ "${1#-}" = "$1" ] && [ "${1%.hip}" = "$1" ]; then REV="$1"; shift; fi
+if [ $# -gt 0 ] && [ "${1%.hip}" != "$1" ]; then SRC="$1"; shift; fi
 OUT="$ROOT/build/asm_cmp"
 rm -rf "$OUT" && mkdir -p "$OUT/prev"
 git -C "$ROOT" archive "$REV" accv-lab_amd/csrc include | tar -x -C "$OUT/prev"
 FLAGS=(-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wall -Wno-unused-function -fno-gpu-rdc -pthread
        --cuda-device-only -S "$@")
 echo "revision: $(git -C "$ROOT" rev-parse --short "$REV") against the working tree"
-echo "command:  (in accv-lab_amd/csrc) hipcc ${FLAGS[*]} draw_heatmap.hip -o <out>.s"
-(cd "$OUT/prev/accv-lab_amd/csrc" && /opt/rocm/bin/hipcc "${FLAGS[@]}" draw_heatmap.hip -o "$OUT/prev.s")
-(cd "$ROOT/accv-lab_amd/csrc" && /opt/rocm/bin/hipcc "${FLAGS[@]}" draw_heatmap.hip -o "$OUT/new.s")
+echo "command:  (in accv-lab_amd/csrc) hipcc ${FLAGS[*]} $SRC -o <out>.s"
+(cd "$OUT/prev/accv-lab_amd/csrc" && /opt/rocm/bin/hipcc "${FLAGS[@]}" "$SRC" -o "$OUT/prev.s")
+(cd "$ROOT/accv-lab_amd/csrc" && /opt/rocm/bin/hipcc "${FLAGS[@]}" "$SRC" -o "$OUT/new.s")
 grep -v __hip_cuid_ "$OUT/prev.s" > "$OUT/prev.nocuid.s"
 grep -v __hip_cuid_ "$OUT/new.s" > "$OUT/new.nocuid.s"
 echo "lines:    $(wc -l < "$OUT/prev.s") at the revision, $(wc -l < "$OUT/new.s") in the working tree"

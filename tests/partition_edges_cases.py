@@ -62,7 +62,7 @@ def grad_out(shape, seed=1):
 
 # ------------------------------------------------------------------------------------------------------ matched_focal_loss
 # name -> (B, Q, C, nqb, qpb or None, dtypes).  Constants of csrc/matched_focal.hip: kTargetElems = 8192, kMaxQ = 1024,
-# kThreads = 256, kFinishThreads = 1024 (16 waves of 64), V = 16 / element size.
+# kThreads = 256, kFinishThreads = 1024 (csrc/matched_pairs.h; 16 waves of 64), V = 16 / element size.
 FOCAL = {
     # 8192 / 8 = 1024 = kMaxQ: the cap is reached, ranges [0, 1024) and [1024, 1030)
     "maxq_two_ranges": (2, 1030, 8, 2, 1024, mf.DTYPES),
@@ -129,7 +129,7 @@ def focal_case(which, dtype, device="cpu"):
 
 
 # -------------------------------------------------------------------------------------------------------- matched_box_loss
-# name -> (B, Q, D, nqb).  Constants of csrc/matched_box.hip: kThreads = 256 queries per workgroup, kFinishThreads = 1024.
+# name -> (B, Q, D, nqb).  Constants of csrc/matched_box.hip: kThreads = 256 queries per workgroup; kFinishThreads = 1024 (csrc/matched_pairs.h).
 BOX = {
     "finish_second_trip": (1, 16400, 4, 65),        # ceil(16400 / 256) = 65 > 64 partials: the lane loop's second trip
     "more_than_1024_frames": (1030, 5, 4, 1),       # the pair count's b += 1024 takes a second trip
