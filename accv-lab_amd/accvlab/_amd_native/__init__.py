@@ -81,6 +81,13 @@ RN_MAX_D = 16
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
+BH_MAX_BOXES = 256
+BH_MAX_CATEGORIES = 128
+BH_TILE_W = 64
+BH_TILE_H = 16
+BH_COUNTS_I64 = 1
+BH_HW_I64 = 2
+BH_CATEGORIES_I64 = 4
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -190,6 +197,9 @@ SIGNATURES = {
     # visible-box selection (params: a VisibleBoxesParams by address; out is bool bytes [B, G])
     "accv_visible_boxes": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp]),
     "accv_visible_boxes_host": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp]),
+    # box-to-heat-map targets (params: a BoxHeatmapParams by address; the map and six per-object outputs)
+    "accv_box_heatmap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_box_heatmap_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # centre-point decoding with circle NMS (params: a CenterPointDecodeParams by address; outputs [T, B, M, ...])
     "accv_center_point_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_center_point_decode_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -273,6 +283,17 @@ class VisibleBoxesParams(ctypes.Structure):
                 ("check_occlusion", ctypes.c_int), ("check_size", ctypes.c_int), ("shrink_to_int", ctypes.c_int)]
 
 
+class BoxHeatmapParams(ctypes.Structure):
+    """accv_box_heatmap_params of include/accv_hip.h"""
+    _fields_ = [("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong), ("map_h", ctypes.c_longlong),
+                ("map_w", ctypes.c_longlong), ("min_fraction_area_clipping", ctypes.c_double), ("min_radius", ctypes.c_double),
+                ("max_radius", ctypes.c_double), ("radius_scaling_factor", ctypes.c_double),
+                ("radius_to_sigma_factor", ctypes.c_double), ("min_object_size", ctypes.c_double * 2),
+                ("num_categories", ctypes.c_int), ("per_category_heatmap", ctypes.c_int), ("has_min_object_size", ctypes.c_int),
+                ("has_per_category_min_object_sizes", ctypes.c_int),
+                ("per_category_min_object_sizes", (ctypes.c_float * 2) * 128), ("k_for_classes", ctypes.c_float * 128)]
+
+
 class CenterPointDecodeParams(ctypes.Structure):
     """accv_center_point_decode_params of include/accv_hip.h"""
     _fields_ = [("scores", ctypes.c_void_p * 8), ("indices", ctypes.c_void_p * 8), ("classes", ctypes.c_void_p * 8),
@@ -310,7 +331,7 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
              "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host",
-             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host"}
+             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host"}
 
 
 def _fast_entry(fn, res, args):

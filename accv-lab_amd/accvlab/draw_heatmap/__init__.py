@@ -18,8 +18,12 @@ indices of every task of a CenterPoint head in one launch), and its inverse at t
 and labels in one launch), and the other NMS of those heads after it: ``rotated_nms_bev`` (rotated BEV-IoU NMS of every
 task's detections in one launch) over ``rotated_iou_bev`` (the pairwise rotated IoU of two ragged BEV box sets).  Ahead of
 the 2D target chain: ``visible_bbox_mask`` / ``select_visible_bboxes`` (which boxes of a camera image are drawn at all: the
-occlusion and minimum-size test of the reference's VisibleBboxSelector in one launch, without a canvas).
+occlusion and minimum-size test of the reference's VisibleBboxSelector in one launch, without a canvas), and the step after
+it: ``boxes_to_heatmap`` (the reference's BoundingBoxToHeatmapConverter: image-space boxes -> scaled and clipped boxes, the
+active decision, integer centres, offsets, sizes, float radii and the per-category Gaussian maps, ``BoxHeatmapTargets``, in
+one launch).
 """
+from .box_heatmap import BoxHeatmapTargets, boxes_to_heatmap
 from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
 from .center_targets import CenterPointTargets, center_point_targets
@@ -36,4 +40,4 @@ __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_a
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
            "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
            "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
-           "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes"]
+           "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets"]

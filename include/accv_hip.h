@@ -489,6 +489,76 @@ int accv_visible_boxes_host(const float* boxes, const float* depths, const void*
                             unsigned flags, long long B, long long G, const accv_visible_boxes_params* params,
                             unsigned char* out);
 
+/* ------------------------------------------------------------------------------------------- box-to-heat-map targets
+ * The step after the visible-box selection: the reference's BoundingBoxToHeatmapConverter
+ * (packages/dali_pipeline_framework/.../processing_steps/bounding_box_to_heatmap_converter.py; its helpers
+ * apply_clipping_and_get_with_clipping_info / get_is_active, operators_impl/python_operator_functions/
+ * python_operator_functions.py:103-252, get_center_from_bboxes / get_radii_from_bboxes, operators_impl/numba_operators/
+ * numba_operators.py:788-905, and the native rasteriser ext_impl/DrawGaussians.cc:32-76) for a ragged batch in ONE launch:
+ * the Gaussian maps and the per-object side outputs a CenterNet-style head trains on.
+ *
+ * boxes: f32 [B, G, 4] contiguous, rows (x1, y1, x2, y2) in image pixels, corners in either order on either diagonal;
+ * centers: f32 [B, G, 2] or null (the box centre); categories: [B, G] int32 (int64 with ACCV_BH_CATEGORIES_I64), needed when
+ * params->num_categories > 0; is_valid: bool bytes [B, G] or null; counts [B] int32 (int64 with ACCV_BH_COUNTS_I64), clamped
+ * to [0, G]: only slots below it are read.  image_hw: null (every frame is params->image_h x image_w) or [B, 2] int32
+ * (int64 with ACCV_BH_HW_I64) rows (H, W), read where the boxes are; either way clamped to [0, 2^24].  Per object, in float32
+ * (the operation sequence is written out in csrc/box_heatmap_arith.h):
+ *   scaling     sx = (float)map_w / (float)W, sy = (float)map_h / (float)H; box and centre coordinates times sx / sy; an
+ *               object with a scaled coordinate that is not finite is inactive and all its outputs are 0
+ *   clipping    each scaled coordinate to [0, map_w - 1] / [0, map_h - 1]: bboxes_heatmap (input corner order) and the
+ *               clipped centre; height_width = (|y2 - y1|, |x2 - x1|) of the clipped box
+ *   centre      center = floor(clipped centre) as (x, y), center_offset = clipped - floor
+ *   radius      min of the four distances from the clipped centre to the clipped box's edges, max(0, .), times
+ *               radius_scaling_factor, clamped to [max(0.5, min_radius), max_radius]
+ *   is_active   finite && (h * w) / (unclipped scaled h * w) >= min_fraction_area_clipping && the size test (h >= min_h &&
+ *               w >= min_w, global or of the object's category) && 0 <= category < num_categories (when num_categories
+ *               > 0) && is_valid; NaN fails every comparison
+ *   drawing     R = (int)ceil(radius), sigma = radius * radius_to_sigma_factor; an active object writes
+ *               k_for_classes[plane] * exp(-(dx^2 + dy^2) / (2 sigma^2)) to the pixels of [cx - R, cx + R] x [cy - R, cy + R]
+ *               inside the map, on plane `category` (plane 0 without per_category_heatmap), combined by max with 0 and
+ *               with the other objects
+ * heatmap: f32 [B, planes, map_h, map_w], planes = num_categories with per_category_heatmap, else 1; every element is
+ * written, nothing is read or cleared beforehand.  Per-object outputs [B, G, ...]: is_active bool bytes, center int32 (x, y),
+ * center_offset f32 (x, y), height_width f32 (h, w), bboxes_heatmap f32 [.., 4], radii f32; slots from counts[b] on are
+ * written as 0.  One workgroup per (frame, plane, ACCV_BH_TILE_W x ACCV_BH_TILE_H tile), no atomics, no workspace, no host
+ * synchronisation, bitwise reproducible.  B == 0 launches nothing; G == 0 still writes the (zero) maps.  Returns ACCV_EINVAL
+ * (null params, negative size, unknown flags, G > ACCV_BH_MAX_BOXES, num_categories outside 0..ACCV_BH_MAX_CATEGORIES, both
+ * minimum-size forms at once, per-category maps or sizes without categories, a map extent outside [1, 2^24], a scalar that
+ * is not finite, max_radius outside (0, 16384], radius_to_sigma_factor <= 0, null or misaligned pointers, more workgroups
+ * than a grid holds) before touching the device, ACCV_ELAUNCH if the launch fails.  accv_box_heatmap_host runs the same
+ * per-object operation sequence serially on host memory and paints with std::exp. */
+#define ACCV_BH_MAX_BOXES 256
+#define ACCV_BH_MAX_CATEGORIES 128
+#define ACCV_BH_TILE_W 64
+#define ACCV_BH_TILE_H 16
+#define ACCV_BH_COUNTS_I64 1u
+#define ACCV_BH_HW_I64 2u
+#define ACCV_BH_CATEGORIES_I64 4u
+/* the scalar parameters and the per-category tables, host memory, read during the call (they travel to the kernel by value) */
+typedef struct accv_box_heatmap_params {
+    long long image_h, image_w;             /* used when image_hw is null */
+    long long map_h, map_w;
+    double min_fraction_area_clipping;
+    double min_radius, max_radius;
+    double radius_scaling_factor;
+    double radius_to_sigma_factor;
+    double min_object_size[2];              /* (h, w), used with has_min_object_size */
+    int num_categories;                     /* 0: categories are not used */
+    int per_category_heatmap;
+    int has_min_object_size;
+    int has_per_category_min_object_sizes;
+    float per_category_min_object_sizes[ACCV_BH_MAX_CATEGORIES][2];   /* (h, w) per category */
+    float k_for_classes[ACCV_BH_MAX_CATEGORIES];                      /* per plane */
+} accv_box_heatmap_params;
+int accv_box_heatmap(const float* boxes, const float* centers, const void* categories, const unsigned char* is_valid,
+                     const void* counts, const void* image_hw, unsigned flags, long long B, long long G,
+                     const accv_box_heatmap_params* params, float* heatmap, unsigned char* is_active, int* center,
+                     float* center_offset, float* height_width, float* bboxes_heatmap, float* radii, void* stream);
+int accv_box_heatmap_host(const float* boxes, const float* centers, const void* categories, const unsigned char* is_valid,
+                          const void* counts, const void* image_hw, unsigned flags, long long B, long long G,
+                          const accv_box_heatmap_params* params, float* heatmap, unsigned char* is_active, int* center,
+                          float* center_offset, float* height_width, float* bboxes_heatmap, float* radii);
+
 /* ------------------------------------------------------------------------------------------------ centre-point decoding
  * The prediction side of a centre-point head, the inverse of accv_center_point_targets: mmdet3d's
  * CenterPointBBoxCoder.decode (core/bbox/coders/centerpoint_bbox_coders.py: the gathers, exp, atan2, the affine map back
