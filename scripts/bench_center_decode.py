@@ -101,7 +101,7 @@ def composition(logits, heads, K):
 
 def timed(fns, warmup, iters, calls):
     """per-call ms of every callable: `iters` blocks of `calls` back-to-back calls each, the sides alternating block by
-    block; median and minimum over the blocks, and the time all blocks of a side took together"""
+    block; median, minimum and maximum over the blocks, and the time all blocks of a side took together"""
     for _ in range(warmup):
         for f in fns.values():
             f()
@@ -117,7 +117,7 @@ def timed(fns, warmup, iters, calls):
             events[k].append((a, b))
         torch.cuda.synchronize()
     ms = {k: [a.elapsed_time(b) / calls for a, b in v] for k, v in events.items()}
-    return {k: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), timed_s=round(sum(v) * calls / 1e3, 3))
+    return {k: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), max_ms=round(max(v), 5), timed_s=round(sum(v) * calls / 1e3, 3))
             for k, v in ms.items()}
 
 

@@ -15,7 +15,8 @@ Three sides alternate inside one process:
                round trips and the serial walk; the decode's output is computed once, as for `nms alone`.
 A timed block is `--calls` back-to-back calls of one side between two device events (the round trip synchronises inside;
 the events still enclose all of its work), its time divided by the number of calls; `--iters` blocks per side; median and
-minimum per call over the blocks.  Launch counts come from torch's profiler in a separate pass (kernel events per call;
+minimum per call over the blocks, for `nms alone` the maximum too (max - min is the spread a change is held against: run
+the script once per library, `ACCV_HIP_LIB` selecting the other build, in turn).  Launch counts come from torch's profiler in a separate pass (kernel events per call;
 copies and memsets are not counted); "not measured" if the profiler is unavailable.  Prints a few lines of log and ONE JSON
 line.
 
@@ -103,7 +104,7 @@ def main():
     lines = [f"rotated_nms_bev  B={args.batch} T={T} N={K} iou_threshold={IOU_THRESHOLD} post_max_size={POST_MAX_SIZE}: {decoded} decoded, {kept} kept"
              f" on {torch.cuda.get_device_name(0)}",
              f"  {args.warmup} warm-up calls, {args.iters} blocks of {args.calls} calls per side, alternating",
-             f"  nms alone           median {ms['nms']['median_ms']:.4f} ms  min {ms['nms']['min_ms']:.4f} ms  launches {show(n_nms)}  host round trips 0",
+             f"  nms alone           median {ms['nms']['median_ms']:.4f} ms  min {ms['nms']['min_ms']:.4f} ms  max {ms['nms']['max_ms']:.4f} ms  launches {show(n_nms)}  host round trips 0",
              f"  peaks+decode+nms    median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {show(n_fused)}  host round trips 0",
              f"  D2H, host nms, H2D  median {ms['round_trip']['median_ms']:.4f} ms  min {ms['round_trip']['min_ms']:.4f} ms  launches {show(n_trip)}  "
              f"host round trips {T} (one per task: 5 copies down, each waiting for the device, and 5 up)",

@@ -225,9 +225,11 @@ def as_numpy(got):
 
 
 # ------------------------------------------------------------------------------------------------- the reference's test
+@functools.lru_cache(None)
 def reference_cases():
     """bounding_box_to_heatmap_converter_test.py of the reference: the eight parametrisations of :288-295 and the two
-    single-map configurations of :446-483, from the data-only fixture; every one expects the same is_active"""
+    single-map configurations of :446-483, from the data-only fixture; every one expects the same is_active.  Built once:
+    the CPU and the GPU module of one pytest process share the cases, as `oracle` demands of cases with one name."""
     g = json.load(open(GOLDEN))
     canon = np.array(g["bboxes"], F)
     common = dict(radius_scaling_factor=g["radius_scaling_factor"])

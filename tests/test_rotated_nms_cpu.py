@@ -1,6 +1,8 @@
 """rotated_iou_bev and rotated_nms_bev through the library's host entries (no GPU): IoU literals with closed forms, random
 frames against the float64 world-coordinate definition of rotated_nms_cases.py, keep decisions ON the threshold where the
-arithmetic is exact, the cuts, argument checks and empty batches."""
+arithmetic is exact, the cuts, argument checks and empty batches; and, at the end, boxes off the dataset-like range
+(rotated_iou_hard_cases.py): yaws many turns from zero, strips, quarter-turn and axis yaws, closed forms that hold the
+definition too, and keep decisions that a single float32 subtraction of the yaws got wrong."""
 import ctypes
 import math
 import os
@@ -368,3 +370,80 @@ def test_the_c_entries_refuse_what_the_python_layer_cannot_produce():
     assert f(None, None, None, None, 0, 3, 3, None) == 0
     assert f(a.data_ptr(), n.data_ptr(), a.data_ptr(), n.data_ptr(), 1 << 40, 1 << 20, 1 << 20, o.data_ptr()) == -1
     assert lib.accv_last_error() == b"rotated_iou_bev (host): sizes overflow"
+
+
+# ----------------------------------------------------------------------------- boxes off the dataset-like range
+import rotated_iou_hard_cases as hard  # noqa: E402
+
+
+@pytest.mark.parametrize("name", hard.NAMES)
+def test_hard_geometry_family_against_the_definition_and_symmetric(name):
+    a, b, want = hard.family(name)
+    got = hard.op_pairs(a, b)
+    err = float(np.abs(got - want).max())
+    assert err <= BAR, f"{name}: IoU off by {err:.3e} (bar {BAR})"
+    sym = float(np.abs(got - hard.op_pairs(b, a)).max())
+    assert sym <= BAR, f"{name}: iou(a, b) and iou(b, a) differ by {sym:.3e}"
+
+
+@pytest.mark.parametrize("form", [hard.crossing_strips, hard.box_inside_box])
+def test_closed_forms_hold_the_definition_and_the_operator(form):
+    """the oracle is trusted on strips and at any relative angle only because it, too, meets forms that do not use it"""
+    a, b, want = form()
+    assert want.min() > 0.005 and want.max() > 0.19
+    assert np.abs(hard.iou64_pairs(a, b) - want).max() <= BAR
+    assert np.abs(np.diag(iou64(a[:64], b[:64])) - want[:64]).max() <= BAR
+    assert np.abs(hard.op_pairs(a, b) - want).max() <= BAR
+    assert np.abs(hard.op_pairs(b, a) - want).max() <= BAR
+
+
+def test_a_rectangle_written_with_its_sides_exchanged_is_the_same_rectangle():
+    r, q, third = hard.rewritten_rectangles()
+    assert (hard.iou64_pairs(r, third) > hard.OVERLAP).mean() > 0.9
+    for pairs in (hard.iou64_pairs, hard.op_pairs):
+        assert pairs(r, q).min() >= 1 - BAR and pairs(q, r).min() >= 1 - BAR, pairs.__name__
+        assert np.abs(pairs(r, third) - pairs(q, third)).max() <= BAR, pairs.__name__
+        assert np.abs(pairs(third, r) - pairs(third, q)).max() <= BAR, pairs.__name__
+
+
+def test_strips_moved_along_their_length_stay_within_the_bar_plus_the_rotation_of_the_centre_offset():
+    """what the bar does not cover, pinned to the bound its cause gives (rotated_iou_hard_cases.py)"""
+    a, b, want, bound = hard.shifted_strips()
+    for got in (hard.op_pairs(a, b), hard.op_pairs(b, a)):
+        err = np.abs(got - want)
+        print(f"strips moved along their length: largest error {err.max():.3e}, largest error / bound {(err / bound).max():.3f}, bound up to {bound.max():.2e}")
+        assert (err <= bound).all(), f"{(err / bound).max():.3f} of the bound"
+
+
+@pytest.mark.parametrize("yaw", [2 * math.pi * 100 + 0.7, -4084.5, hard.YAW_DOMAIN])
+def test_identical_boxes_many_turns_out_still_give_one_exactly(yaw):
+    """equal yaws leave no rounding to correct: the relative angle is +0 and its cosine 1, as before the correction"""
+    for box in ((10.0, 20.0, 4.5, 1.9, yaw), (-37.25, 48.5, 50.0, 0.02, yaw)):
+        assert one(box, box) == 1.0
+
+
+def test_beyond_the_yaw_domain_the_value_is_still_a_finite_number_in_0_1():
+    a = np.float32([[1.0, 2.0, 4.5, 1.9, 2 * math.pi * 1e5 + 0.3], [1.0, 2.0, 4.5, 1.9, 3e38], [1.0, 2.0, 50.0, 0.02, -1e9], [1.0, 2.0, 4.5, 1.9, 0.3]])
+    b = a.copy()
+    b[:, 4] = np.float32([0.3, -3e38, 1e9, -2 * math.pi * 1e5])
+    m = iou(a, b)
+    assert np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()
+
+
+def test_the_frozen_pairs_are_what_their_records_say():
+    for a, b, want, was in hard.FROZEN:
+        assert abs(hard.iou64_pairs(np.float32([a]), np.float32([b]))[0] - want) < 1e-12
+        assert abs(was - want) > 3e-5 and a[0] < -10 and a[1] < -10 and b[0] < -10 and b[1] < -10
+    assert {was > want for _, _, want, was in hard.FROZEN} == {True, False}, "both wrong directions"
+
+
+@pytest.mark.parametrize("k", range(len(hard.FROZEN)))
+def test_keep_decisions_that_one_float32_subtraction_of_the_yaws_got_wrong(k):
+    """the threshold lies 2e-5 from the float64 IoU, twice the margin, on the side where the old arithmetic's value was"""
+    a, b, want, was = hard.FROZEN[k]
+    thr = hard.frozen_threshold(want, was)
+    case = placed_case(70, {63: b, 64: a})
+    assert_margin(case, [thr])
+    got = rotated_nms_bev(case.detections(), thr)
+    check(got, definition(case, [thr]), case, f"frozen pair {k}")
+    assert kept_slots(got) == [s for s in range(70) if s != 64 or want <= thr]

@@ -1,8 +1,9 @@
 """rotated_nms_bev and rotated_iou_bev on the GPU: the kernels against the float64 world-coordinate definition of
 rotated_nms_cases.py and against the host entries, at the edges of their work partition (wave block, chunk of kThreads slots,
 IoU tile, the two cuts), keep decisions ON the threshold across those edges, guard bands, reproducibility, graph capture, no
-host synchronisation, a non-default stream, and the path heatmap_peaks -> center_point_decode -> rotated_nms_bev.  The
-largest IoU error seen against the definition goes to profiles/rotated_nms_accuracy.log."""
+host synchronisation, a non-default stream, and the path heatmap_peaks -> center_point_decode -> rotated_nms_bev; the
+hard-geometry families of rotated_iou_hard_cases.py against the definition and the host.  The largest IoU error seen against
+the definition, per case, goes to profiles/rotated_nms_accuracy.log."""
 import ctypes
 import os
 import re
@@ -17,6 +18,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from rotated_nms_cases import (BAR, BEV, BIG, CHAIN, CHAIN_THR, SMALL, Case, assert_margin, check, definition, iou64, kept_slots,  # noqa: E402
                                make_case, pick_threshold, placed_case, ragged5, random_boxes, share)
+
+import rotated_iou_hard_cases as hard  # noqa: E402
 
 from accvlab.batching_helpers import RaggedBatch  # noqa: E402
 from accvlab.draw_heatmap import (CenterPointDetections, center_point_decode, gather_at_centers, heatmap_peaks, rotated_iou_bev,  # noqa: E402
@@ -38,7 +41,9 @@ THREADS = int(_constant(_SRC, "kThreads"))          # slots per chunk
 TILE = int(_constant(_SRC, "kTile"))
 assert (WAVE, THREADS, TILE) == (64, 256, 64)
 BELOW = float(np.nextafter(np.float32(0.25), np.float32(0)))
-IOU_CASES = 7      # comparisons of rotated_iou_bev with the definition in this module: four matrix shapes and three box kinds
+# comparisons of rotated_iou_bev with the definition in this module: four matrix shapes, three box kinds and the families of
+# rotated_iou_hard_cases.py
+IOU_CASES = 7 + len(hard.NAMES)
 
 
 def both(case, thr, what="", **kw):
@@ -230,6 +235,65 @@ def test_iou_of_a_frame_of_nms_size_and_the_closed_forms_on_the_device(accuracy)
     lit = ragged5([[BIG, SMALL, (3.0, 4.0, 10.0, 2.8, 1e-4), (2.0, 1.0, 4.0, 2.0, 0.0), (6.0, 1.0, 4.0, 2.0, 0.0)]], [5], DEV)
     g = rotated_iou_bev(lit, lit).tensor[0].cpu().numpy()
     assert g[0, 1] == 0.25 and g[1, 0] == 0.25 and (np.diag(g) == 1.0).all() and g[3, 4] == 0.0 and g[4, 3] == 0.0
+
+
+# ------------------------------------------------------------------------------------- boxes off the dataset-like range
+@pytest.mark.parametrize("name", hard.NAMES)
+def test_hard_geometry_family_on_the_device(name, accuracy):
+    """yaws many turns out, strips, quarter-turn and axis yaws, far centres: against the definition, against the host entry (the
+    same operations but the platform's cosf / sinf), and iou(a, b) against iou(b, a)"""
+    a, b, want = hard.family(name)
+    got = hard.op_pairs(a, b, DEV)
+    err = float(np.abs(got - want).max())
+    accuracy.append((name, len(want), int((want > hard.OVERLAP).sum()), err))
+    assert err <= BAR, f"{name}: IoU off by {err:.3e} (bar {BAR})"
+    host = float(np.abs(got - hard.op_pairs(a, b)).max())
+    assert host <= BAR, f"{name}: device against host {host:.3e}"
+    sym = float(np.abs(got - hard.op_pairs(b, a, DEV)).max())
+    assert sym <= BAR, f"{name}: iou(a, b) and iou(b, a) differ by {sym:.3e}"
+
+
+def test_closed_forms_and_rewritten_rectangles_on_the_device():
+    for form in (hard.crossing_strips, hard.box_inside_box):
+        a, b, want = form()
+        assert np.abs(hard.op_pairs(a, b, DEV) - want).max() <= BAR, form.__name__
+        assert np.abs(hard.op_pairs(b, a, DEV) - want).max() <= BAR, form.__name__
+    r, q, third = hard.rewritten_rectangles()
+    assert hard.op_pairs(r, q, DEV).min() >= 1 - BAR and hard.op_pairs(q, r, DEV).min() >= 1 - BAR
+    assert np.abs(hard.op_pairs(r, third, DEV) - hard.op_pairs(q, third, DEV)).max() <= BAR
+    assert np.abs(hard.op_pairs(third, r, DEV) - hard.op_pairs(third, q, DEV)).max() <= BAR
+
+
+def test_strips_moved_along_their_length_stay_within_the_bar_plus_the_rotation_of_the_centre_offset():
+    """what the bar does not cover, pinned to the bound its cause gives (rotated_iou_hard_cases.py)"""
+    a, b, want, bound = hard.shifted_strips()
+    for got in (hard.op_pairs(a, b, DEV), hard.op_pairs(b, a, DEV)):
+        err = np.abs(got - want)
+        print(f"strips moved along their length: largest error {err.max():.3e}, largest error / bound {(err / bound).max():.3f}, bound up to {bound.max():.2e}")
+        assert (err <= bound).all(), f"{(err / bound).max():.3f} of the bound"
+
+
+def test_many_turns_out_identical_boxes_give_one_exactly_and_beyond_the_domain_a_finite_value():
+    same = np.float32([[10.0, 20.0, 4.5, 1.9, 628.3], [-37.25, 48.5, 50.0, 0.02, -4084.5], [1.0, 2.0, 4.5, 1.9, hard.YAW_DOMAIN]])
+    assert (hard.op_pairs(same, same, DEV) == 1.0).all()
+    a = np.float32([[1.0, 2.0, 4.5, 1.9, 2 * np.pi * 1e5 + 0.3], [1.0, 2.0, 4.5, 1.9, 3e38], [1.0, 2.0, 50.0, 0.02, -1e9], [1.0, 2.0, 4.5, 1.9, 0.3]])
+    b = a.copy()
+    b[:, 4] = np.float32([0.3, -3e38, 1e9, -2 * np.pi * 1e5])
+    r = ragged5(a[None], [4], DEV), ragged5(b[None], [4], DEV)
+    m = rotated_iou_bev(*r).tensor.cpu().numpy()
+    assert np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()
+
+
+@pytest.mark.parametrize("edge", [WAVE, THREADS])
+@pytest.mark.parametrize("k", range(len(hard.FROZEN)))
+def test_keep_decisions_that_one_float32_subtraction_of_the_yaws_got_wrong_across_a_boundary(k, edge):
+    """the threshold lies 2e-5 from the float64 IoU, twice the margin, on the side where the old arithmetic's value was"""
+    a, b, want, was = hard.FROZEN[k]
+    thr = hard.frozen_threshold(want, was)
+    N = edge + WAVE
+    case = placed_case(N, {edge - 1: b, edge: a})
+    got, _ = both(case, thr, f"frozen pair {k}")
+    assert kept_slots(got) == [s for s in range(N) if s != edge or want <= thr]
 
 
 # ------------------------------------------------------------------------------------------------------------ guard bands
