@@ -88,6 +88,11 @@ BH_TILE_H = 16
 BH_COUNTS_I64 = 1
 BH_HW_I64 = 2
 BH_CATEGORIES_I64 = 4
+IP_MAX_EXTENT = 16384
+IP_TILE_W = 64
+IP_TILE_H = 16
+IP_LAYOUT_CHW = 0
+IP_LAYOUT_HWC = 1
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -200,6 +205,9 @@ SIGNATURES = {
     # box-to-heat-map targets (params: a BoxHeatmapParams by address; the map and six per-object outputs)
     "accv_box_heatmap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_box_heatmap_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # camera-image preparation (params: a PrepareImagesParams by address; the host entry also takes the coords output)
+    "accv_prepare_images": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_prepare_images_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # centre-point decoding with circle NMS (params: a CenterPointDecodeParams by address; outputs [T, B, M, ...])
     "accv_center_point_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_center_point_decode_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -294,6 +302,15 @@ class BoxHeatmapParams(ctypes.Structure):
                 ("per_category_min_object_sizes", (ctypes.c_float * 2) * 128), ("k_for_classes", ctypes.c_float * 128)]
 
 
+class PrepareImagesParams(ctypes.Structure):
+    """accv_prepare_images_params of include/accv_hip.h"""
+    _fields_ = [("batch", ctypes.c_longlong), ("source_h", ctypes.c_longlong), ("source_w", ctypes.c_longlong),
+                ("output_h", ctypes.c_longlong), ("output_w", ctypes.c_longlong), ("tile_h", ctypes.c_longlong),
+                ("tile_w", ctypes.c_longlong), ("mean", ctypes.c_double * 3), ("std", ctypes.c_double * 3),
+                ("pad_before_normalize", ctypes.c_int), ("is_bgr", ctypes.c_int), ("layout", ctypes.c_int),
+                ("dtype", ctypes.c_int), ("source_hw_i64", ctypes.c_int)]
+
+
 class CenterPointDecodeParams(ctypes.Structure):
     """accv_center_point_decode_params of include/accv_hip.h"""
     _fields_ = [("scores", ctypes.c_void_p * 8), ("indices", ctypes.c_void_p * 8), ("classes", ctypes.c_void_p * 8),
@@ -331,7 +348,8 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
              "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host",
-             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host"}
+             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host",
+             "accv_prepare_images_host"}
 
 
 def _fast_entry(fn, res, args):

@@ -559,6 +559,64 @@ int accv_box_heatmap_host(const float* boxes, const float* centers, const void* 
                           const accv_box_heatmap_params* params, float* heatmap, unsigned char* is_active, int* center,
                           float* center_offset, float* height_width, float* bboxes_heatmap, float* radii);
 
+/* ------------------------------------------------------------------------------------------ camera-image preparation
+ * The image side of the reference's camera pipeline (packages/dali_pipeline_framework/.../processing_steps/: AffineTransformer
+ * through fn.warp_affine with bilinear interpolation and fill 0, PhotoMetricDistorter._process_images,
+ * ImageToTileSizePadder, ImageMeanStdDevNormalizer / ImageRange01Normalizer; four DALI operators and four passes there) for a
+ * batch of decoded images in ONE launch: the uint8 source is read where it is sampled, the float result is written once.
+ *
+ * images: u8 [batch, source_h, source_w, 3] contiguous.  source_hw: null or [batch, 2] int32 (int64 with
+ * params->source_hw_i64) rows (H, W), read where the images are and clamped to [0, source_h] x [0, source_w]: the valid region
+ * of each image; bytes outside it are never read and count as outside the image.  transforms: null or f32 [batch, 2, 3],
+ * the FORWARD map [[a, b, tx], [c, d, ty]] from source to output coordinates (pixel i covers [i, i + 1), its centre is at
+ * i + 0.5); null takes source pixel (X, Y) as is and needs output = source extent.  photometric: null or f32 [batch, 6] rows
+ * (delta, alpha_pre, saturation, hue_degrees, alpha_post, permutation_index).  Per output pixel, in float32 (the operation
+ * sequence is written out in csrc/image_prep_arith.h):
+ *   position    det = a * d - b * c; u = X + 0.5 - tx, v = Y + 0.5 - ty; sx = (d * u - b * v) / det - 0.5,
+ *               sy = (a * v - c * u) / det - 0.5; an image whose matrix entries, det or 1 / det are not finite, or det == 0,
+ *               is outside everywhere
+ *   sample      bilinear over the four neighbours of (floor(sx), floor(sy)); a neighbour outside the valid region is 0;
+ *               the range is checked before any float -> int conversion
+ *   colour      v = value / 255; clamp(v + delta); clamp(v * alpha_pre); saturation (multiplied, not clamped) and hue
+ *               (degrees, mod 360) in HSV space, the channel order from params->is_bgr; clamp(v * alpha_post); the channel
+ *               permutation of get_color_channel_permutation (an index outside 0..5 is 0); clamp(v); clamp is to [0, 1];
+ *               a stage whose value is the identity (0, 1, 1 and 0, 1) is skipped, so an identity row equals null bit for bit
+ *   normalise   out = (255 * v - mean[k]) / std[k] per OUTPUT channel k, folded to v * scale + bias (float64, rounded once)
+ *   padding     the output extent is (ceil(output_h / tile_h) * tile_h, likewise w); padding pixels hold (0 - mean) / std
+ *               with pad_before_normalize (the padder in front of the normaliser), else 0
+ * out: [batch, 3, Hp, Wp] (ACCV_IP_LAYOUT_CHW) or [batch, Hp, Wp, 3] (ACCV_IP_LAYOUT_HWC) of dtype 0 f32, 1 f16, 2 bf16 (the
+ * float32 result rounded once to nearest even); every element is written exactly once, nothing is read or cleared.  One
+ * workgroup per (image, ACCV_IP_TILE_W x ACCV_IP_TILE_H tile of the padded output), 4 consecutive x per lane, stores of 16
+ * bytes (8 for the 16-bit types) when Wp % 4 == 0 and out is aligned to the store, else per element; no workspace, no
+ * atomics, no host synchronisation, bitwise reproducible.  batch == 0 launches nothing.  Returns ACCV_EINVAL (null params,
+ * negative batch, an extent or tile outside [1, ACCV_IP_MAX_EXTENT], output != source extent without transforms, unknown
+ * layout or dtype, mean / std not finite or std <= 0, null or misaligned pointers, more workgroups than a grid holds) before
+ * touching the device, ACCV_ELAUNCH if the launch fails.  accv_prepare_images_host runs the same operation sequence serially
+ * on host memory and is bit-equal; coords, when not null, receives f32 [batch, output_h, output_w, 4] rows (x0, y0, wx, wy):
+ * the sample position of every output pixel, (-2, -2, 0, 0) where no neighbour can lie inside. */
+#define ACCV_IP_MAX_EXTENT 16384
+#define ACCV_IP_TILE_W 64
+#define ACCV_IP_TILE_H 16
+#define ACCV_IP_LAYOUT_CHW 0
+#define ACCV_IP_LAYOUT_HWC 1
+/* host memory, read during the call */
+typedef struct accv_prepare_images_params {
+    long long batch;
+    long long source_h, source_w;           /* of the images tensor */
+    long long output_h, output_w;           /* before padding */
+    long long tile_h, tile_w;               /* the output is padded to multiples of these; 1: no padding */
+    double mean[3], std[3];                 /* in 0..255 units, output-channel order */
+    int pad_before_normalize;
+    int is_bgr;
+    int layout;                             /* ACCV_IP_LAYOUT_* */
+    int dtype;                              /* 0 f32, 1 f16, 2 bf16 */
+    int source_hw_i64;
+} accv_prepare_images_params;
+int accv_prepare_images(const unsigned char* images, const void* source_hw, const float* transforms, const float* photometric,
+                        const accv_prepare_images_params* params, void* out, void* stream);
+int accv_prepare_images_host(const unsigned char* images, const void* source_hw, const float* transforms,
+                             const float* photometric, const accv_prepare_images_params* params, void* out, float* coords);
+
 /* ------------------------------------------------------------------------------------------------ centre-point decoding
  * The prediction side of a centre-point head, the inverse of accv_center_point_targets: mmdet3d's
  * CenterPointBBoxCoder.decode (core/bbox/coders/centerpoint_bbox_coders.py: the gathers, exp, atan2, the affine map back
