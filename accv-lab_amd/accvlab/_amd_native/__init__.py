@@ -70,6 +70,11 @@ CT_MAX_CLASSES = 64
 CT_NO_TASK = 255
 CT_LABELS_I64 = 1
 CT_COUNTS_I64 = 2
+BA_MAX_POINT_TRANSFORMS = 4
+BA_MAX_FRAME_TRANSFORMS = 2
+BA_COUNTS_I64 = 1
+BA_LABELS_I64 = 2
+BA_RANGE_ON_OUTPUT = 4
 CD_MAX_TASKS = 8
 CD_MAX_MAPS = 8
 CD_MAX_CLASSES = 64
@@ -199,6 +204,9 @@ SIGNATURES = {
                                        _vp]),
     "accv_center_point_targets_host": (_i, [_vp, _vp, _vp, _u, _ll, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
+    # BEV box augmentation + range filter (params: a BevAugmentParams by address; outputs [B, N, ...])
+    "accv_bev_augment": (_i, [_vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_bev_augment_host": (_i, [_vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     # visible-box selection (params: a VisibleBoxesParams by address; out is bool bytes [B, G])
     "accv_visible_boxes": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp]),
     "accv_visible_boxes_host": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp]),
@@ -285,6 +293,14 @@ class CenterPointTargetsParams(ctypes.Structure):
                 ("class_pos", ctypes.c_ubyte * 64)]
 
 
+class BevAugmentParams(ctypes.Structure):
+    """accv_bev_augment_params of include/accv_hip.h"""
+    _fields_ = [("range_min", ctypes.c_double * 3), ("range_max", ctypes.c_double * 3), ("point_in", ctypes.c_void_p * 4),
+                ("point_out", ctypes.c_void_p * 4), ("point_count", ctypes.c_longlong * 4), ("frame_in", ctypes.c_void_p * 2),
+                ("frame_out", ctypes.c_void_p * 2), ("frame_count", ctypes.c_longlong * 2), ("point_rows", ctypes.c_int * 4),
+                ("num_point_transforms", ctypes.c_int), ("num_frame_transforms", ctypes.c_int), ("has_range", ctypes.c_int)]
+
+
 class VisibleBoxesParams(ctypes.Structure):
     """accv_visible_boxes_params of include/accv_hip.h"""
     _fields_ = [("minimum_size", ctypes.c_double), ("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong),
@@ -347,7 +363,8 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
              "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
              "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
-             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_center_point_decode_host",
+             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_bev_augment_host",
+             "accv_center_point_decode_host",
              "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host",
              "accv_prepare_images_host"}
 

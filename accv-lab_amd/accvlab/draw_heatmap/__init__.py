@@ -21,8 +21,12 @@ the 2D target chain: ``visible_bbox_mask`` / ``select_visible_bboxes`` (which bo
 occlusion and minimum-size test of the reference's VisibleBboxSelector in one launch, without a canvas), and the step after
 it: ``boxes_to_heatmap`` (the reference's BoundingBoxToHeatmapConverter: image-space boxes -> scaled and clipped boxes, the
 active decision, integer centres, offsets, sizes, float radii and the per-category Gaussian maps, ``BoxHeatmapTargets``, in
-one launch).
+one launch).  Ahead of the 3D target chain: ``bev_augment_boxes`` (the reference's BEVBBoxesTransformer3D, PointsInRangeCheck
+and ConditionalElementRemover: raw ragged 3D boxes and the matrices of their frame -> rotated, scaled and translated boxes,
+range-filtered and compacted, ``BevAugmented``, in one launch; ``bev_augmentation_params`` / ``sample_bev_augmentation``
+build its parameter rows).
 """
+from .bev_augment import BevAugmented, bev_augment_boxes, bev_augmentation_params, sample_bev_augmentation
 from .box_heatmap import BoxHeatmapTargets, boxes_to_heatmap
 from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
@@ -40,4 +44,5 @@ __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_a
            "draw_heatmap_multiscale", "draw_polylines_multiscale", "draw_targets_multiscale", "sample_lane_targets", "sample_lanes",
            "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
            "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
-           "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets"]
+           "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets",
+           "bev_augment_boxes", "BevAugmented", "bev_augmentation_params", "sample_bev_augmentation"]

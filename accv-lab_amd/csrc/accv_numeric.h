@@ -234,6 +234,26 @@ __device__ __forceinline__ void block_sum(T& a, U& b)
     }
 }
 
+// The order-preserving rank of a workgroup of kWaves waves of 64 (center_targets.hip, bev_augment.hip): the number of set
+// predicates in lower threads of the workgroup (`before`) and in the whole workgroup (`total`); a __ballot + popcount
+// inside the wave, the waves' totals in s_cnt[kWaves] (LDS); one barrier.  s_cnt is read between this barrier and the next
+// one of the workgroup, so a caller that alternates two rows never writes a row that a slower wave still reads.
+template <int kWaves>
+__device__ __forceinline__ void block_rank(bool on, int* s_cnt, int lane, int wave, int& before, int& total)
+{
+    const unsigned long long bits = __ballot(on);
+    if (lane == 0) s_cnt[wave] = __popcll(bits);
+    __syncthreads();
+    before = __popcll(bits & ((1ull << lane) - 1ull));
+    total = 0;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) {
+        const int c = s_cnt[v];
+        total += c;
+        if (v < wave) before += c;
+    }
+}
+
 // The denominator of a mean-reduced loss, in the type of avg_value: the caller's value, the caller's device scalar, or
 // max(count, 1) (count.clamp(min=1)).
 template <class F>

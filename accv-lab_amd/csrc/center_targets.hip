@@ -94,24 +94,8 @@ __host__ __device__ inline void write_padding(const Args& a, long long row0, lon
 }
 
 // ------------------------------------------------------------------------------------------------------------- device
-// the number of set predicates in lower threads of the workgroup (`before`) and in the whole workgroup (`total`); one
-// barrier.  s_cnt is read between this barrier and the next one of the workgroup, so a caller that alternates two rows
-// (candidates, kept) never writes a row that a slower wave still reads.
-__device__ __forceinline__ void block_rank(bool on, int* s_cnt, int lane, int wave, int& before, int& total)
-{
-    const unsigned long long bits = __ballot(on);
-    if (lane == 0) s_cnt[wave] = __popcll(bits);
-    __syncthreads();
-    before = __popcll(bits & ((1ull << lane) - 1ull));
-    total = 0;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) {
-        const int c = s_cnt[v];
-        total += c;
-        if (v < wave) before += c;
-    }
-}
-
+// accv::block_rank (accv_numeric.h) is called on two alternating rows (candidates, kept), so neither is written while a
+// slower wave still reads it
 __global__ __launch_bounds__(kThreads) void center_point_targets_kernel(const Args a)
 {
     __shared__ int s_cand[kWaves], s_keep[kWaves];
@@ -129,10 +113,10 @@ __global__ __launch_bounds__(kThreads) void center_point_targets_kernel(const Ar
         float cx = 0.0f, cy = 0.0f, w = 0.0f, l = 0.0f;
         const bool valid = pos >= 0 && scale_and_test(a.k, box[0], box[1], box[3], box[4], cx, cy, w, l);
         int before, total;
-        block_rank(pos >= 0, s_cand, lane, wave, before, total);
+        accv::block_rank<kWaves>(pos >= 0, s_cand, lane, wave, before, total);
         const bool keep = valid && cands + before < a.max_objs;
         cands += total;
-        block_rank(keep, s_keep, lane, wave, before, total);
+        accv::block_rank<kWaves>(keep, s_keep, lane, wave, before, total);
         const long long slot = kept + before;
         kept += total;
         if (keep && slot < a.M) write_object(a, row0, slot, n, box, pos, cx, cy, w, l);

@@ -448,6 +448,60 @@ int accv_center_point_targets_host(const float* boxes, const void* labels, const
                                    const accv_center_point_targets_params* params, int* centers, int* radii,
                                    int* out_labels, float* targets, long long* indices, int* source, long long* out_sizes);
 
+/* --------------------------------------------------------------------------------- BEV box augmentation + range filter
+ * What the raw 3D boxes of a sample go through before accv_center_point_targets, for a ragged batch in ONE launch: the
+ * reference's BEVBBoxesTransformer3D (packages/dali_pipeline_framework/.../processing_steps/bev_bboxes_transformer_3d.py:
+ * a global rotation about z, then a uniform scaling, then a translation of centres, sizes, yaws and velocities, and the
+ * update of every matrix that maps to or from the augmented frame), PointsInRangeCheck on the centres
+ * (processing_steps/points_in_range_check.py; check_points_in_box of operators_impl/numba_operators) and the
+ * ConditionalElementRemover over the resulting is_active flag; wired at examples/pipeline_setup/stream_petr_pipeline.py:409-497.
+ *
+ * boxes: f32 [B, N, D] contiguous, D = 7 or 9 as (x, y, z, dx, dy, dz, yaw[, vx, vy]); rows: f32 [B, 7], the frame's
+ * (angle, cos, sin, scale, tx, ty, tz), the cosine and sine read as given; labels: null or [B, N] int32 (int64 with
+ * ACCV_BA_LABELS_I64); valid: null or bool bytes [B, N], the rest of the keep condition; counts [B] int32 (int64 with
+ * ACCV_BA_COUNTS_I64), clamped to [0, N]: only slots below it are read.  A slot is kept iff valid and, with
+ * params->has_range, range_min <= centre <= range_max on all three coordinates (the float32 centre against the float64
+ * borders as the reference compares them, both inclusive, NaN fails, +-inf allowed), tested on the raw centre or, with
+ * ACCV_BA_RANGE_ON_OUTPUT, on the augmented one.
+ * The float32 operation sequence is written out in csrc/bev_augment_arith.h (nothing contracted, division correctly
+ * rounded).  params->point_in[i]: f32 [B, point_count[i], point_rows[i] = 3 or 4, 4], matrices applied to points of the
+ * augmented frame, M . A^-1 written to point_out[i]; params->frame_in[i]: f32 [B, frame_count[i], 4, 4], matrices whose
+ * results are points of that frame, A . M written to frame_out[i]; A = T . S . R.  Inputs and outputs do not overlap.
+ * Outputs: out_boxes f32 [B, N, D], the kept boxes augmented and compacted in ascending slot order; out_labels [B, N] of
+ * the labels' type (null without labels); source int32 [B, N], the input slot; keep bool bytes [B, N] over the INPUT
+ * slots; out_sizes int64 [B], the kept count.  Slots kept .. N-1 are written too: 0 everywhere, source -1, and keep is 0
+ * from counts[b] on (a complete write).  One workgroup per frame, no atomics, no workspace, no host synchronisation,
+ * bitwise reproducible and bit-equal to accv_bev_augment_host, which runs the same operation sequence serially on host
+ * memory.  B == 0 launches nothing and writes nothing.  Returns ACCV_EINVAL (null params, negative size, D not 7 / 9,
+ * unknown flags, more transforms than the maxima, matrices of other than 3 or 4 rows, N above 2^31 - 1, null or misaligned
+ * pointers, labels without out_labels) before touching the device, ACCV_ELAUNCH if the launch fails. */
+#define ACCV_BA_MAX_POINT_TRANSFORMS 4
+#define ACCV_BA_MAX_FRAME_TRANSFORMS 2
+#define ACCV_BA_COUNTS_I64 1u
+#define ACCV_BA_LABELS_I64 2u
+#define ACCV_BA_RANGE_ON_OUTPUT 4u
+/* the range and the matrix tensors, host memory, read during the call */
+typedef struct accv_bev_augment_params {
+    double range_min[3], range_max[3];   /* used with has_range */
+    const float* point_in[ACCV_BA_MAX_POINT_TRANSFORMS];
+    float* point_out[ACCV_BA_MAX_POINT_TRANSFORMS];
+    long long point_count[ACCV_BA_MAX_POINT_TRANSFORMS];   /* K, matrices per frame */
+    const float* frame_in[ACCV_BA_MAX_FRAME_TRANSFORMS];
+    float* frame_out[ACCV_BA_MAX_FRAME_TRANSFORMS];
+    long long frame_count[ACCV_BA_MAX_FRAME_TRANSFORMS];   /* K, matrices per frame */
+    int point_rows[ACCV_BA_MAX_POINT_TRANSFORMS];          /* R = 3 or 4 */
+    int num_point_transforms;
+    int num_frame_transforms;
+    int has_range;
+} accv_bev_augment_params;
+int accv_bev_augment(const float* boxes, const float* rows, const void* labels, const unsigned char* valid, const void* counts,
+                     unsigned flags, long long B, long long N, long long D, const accv_bev_augment_params* params,
+                     float* out_boxes, void* out_labels, int* source, unsigned char* keep, long long* out_sizes, void* stream);
+int accv_bev_augment_host(const float* boxes, const float* rows, const void* labels, const unsigned char* valid,
+                          const void* counts, unsigned flags, long long B, long long N, long long D,
+                          const accv_bev_augment_params* params, float* out_boxes, void* out_labels, int* source,
+                          unsigned char* keep, long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------------ visible-box selection
  * Which 2D boxes of a camera image are drawn at all: the occlusion test and the minimum-size test of the reference's
  * VisibleBboxSelector step (packages/dali_pipeline_framework/.../processing_steps/visible_bbox_selector.py; the operators
