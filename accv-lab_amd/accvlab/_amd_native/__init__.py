@@ -86,6 +86,11 @@ RN_MAX_D = 16
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
+CB_MAX_BOXES = 256
+CB_MAX_MATRICES = 4
+CB_COUNTS_I64 = 1
+CB_HW_I64 = 2
+CB_CATEGORIES_I64 = 4
 BH_MAX_BOXES = 256
 BH_MAX_CATEGORIES = 128
 BH_TILE_W = 64
@@ -210,6 +215,9 @@ SIGNATURES = {
     # visible-box selection (params: a VisibleBoxesParams by address; out is bool bytes [B, G])
     "accv_visible_boxes": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp]),
     "accv_visible_boxes_host": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp]),
+    # camera-box augmentation (params: a CameraBoxesParams by address; outputs [F, G, ...])
+    "accv_camera_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_camera_boxes_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # box-to-heat-map targets (params: a BoxHeatmapParams by address; the map and six per-object outputs)
     "accv_box_heatmap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_box_heatmap_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -307,6 +315,15 @@ class VisibleBoxesParams(ctypes.Structure):
                 ("check_occlusion", ctypes.c_int), ("check_size", ctypes.c_int), ("shrink_to_int", ctypes.c_int)]
 
 
+class CameraBoxesParams(ctypes.Structure):
+    """accv_camera_boxes_params of include/accv_hip.h"""
+    _fields_ = [("minimum_size", ctypes.c_double), ("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong),
+                ("image_hw", ctypes.c_void_p), ("mat_in", ctypes.c_void_p * 4), ("mat_out", ctypes.c_void_p * 4),
+                ("mat_count", ctypes.c_longlong * 4), ("mat_rows", ctypes.c_int * 4), ("mat_cols", ctypes.c_int * 4),
+                ("num_matrices", ctypes.c_int), ("check_occlusion", ctypes.c_int), ("check_size", ctypes.c_int),
+                ("shrink_to_int", ctypes.c_int), ("crop", ctypes.c_int), ("order_corners", ctypes.c_int)]
+
+
 class BoxHeatmapParams(ctypes.Structure):
     """accv_box_heatmap_params of include/accv_hip.h"""
     _fields_ = [("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong), ("map_h", ctypes.c_longlong),
@@ -366,6 +383,7 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_bev_augment_host",
              "accv_center_point_decode_host",
              "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host",
+             "accv_camera_boxes_host",
              "accv_prepare_images_host"}
 
 

@@ -21,13 +21,18 @@ the 2D target chain: ``visible_bbox_mask`` / ``select_visible_bboxes`` (which bo
 occlusion and minimum-size test of the reference's VisibleBboxSelector in one launch, without a canvas), and the step after
 it: ``boxes_to_heatmap`` (the reference's BoundingBoxToHeatmapConverter: image-space boxes -> scaled and clipped boxes, the
 active decision, integer centres, offsets, sizes, float radii and the per-category Gaussian maps, ``BoxHeatmapTargets``, in
-one launch).  Ahead of the 3D target chain: ``bev_augment_boxes`` (the reference's BEVBBoxesTransformer3D, PointsInRangeCheck
+one launch), and the step in front of both: ``camera_augment_boxes`` (the annotation side of the reference's AffineTransformer,
+its VisibleBboxSelector, the ``categories >= 0 and is_visible`` condition, the ConditionalElementRemover and the two
+CoordinateCroppers: raw ragged 2D boxes, centres, depths and categories and the image matrix of their frame -> warped,
+visibility-filtered, compacted and cropped annotations and updated projection matrices, ``CameraBoxes``, in one launch).
+Ahead of the 3D target chain: ``bev_augment_boxes`` (the reference's BEVBBoxesTransformer3D, PointsInRangeCheck
 and ConditionalElementRemover: raw ragged 3D boxes and the matrices of their frame -> rotated, scaled and translated boxes,
 range-filtered and compacted, ``BevAugmented``, in one launch; ``bev_augmentation_params`` / ``sample_bev_augmentation``
 build its parameter rows).
 """
 from .bev_augment import BevAugmented, bev_augment_boxes, bev_augmentation_params, sample_bev_augmentation
 from .box_heatmap import BoxHeatmapTargets, boxes_to_heatmap
+from .camera_boxes import CameraBoxes, camera_augment_boxes
 from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
 from .center_targets import CenterPointTargets, center_point_targets
@@ -45,4 +50,5 @@ __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_a
            "gaussian_focal_loss", "heatmap_peaks", "HeatmapPeaks", "gather_at_centers", "center_regression_loss",
            "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
            "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets",
-           "bev_augment_boxes", "BevAugmented", "bev_augmentation_params", "sample_bev_augmentation"]
+           "bev_augment_boxes", "BevAugmented", "bev_augmentation_params", "sample_bev_augmentation",
+           "camera_augment_boxes", "CameraBoxes"]

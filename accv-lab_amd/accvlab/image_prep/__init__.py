@@ -1,8 +1,15 @@
 """accvlab.image_prep — (extension) the image side of the reference's camera pipeline (packages/dali_pipeline_framework:
 AffineTransformer, PhotoMetricDistorter, ImageToTileSizePadder, ImageMeanStdDevNormalizer / ImageRange01Normalizer) as one
-HIP launch on the MI355X: ``prepare_images`` and the host-side helpers that build its parameters."""
+HIP launch on the MI355X: ``prepare_images`` and the host-side helpers that build its parameters, among them
+``sample_image_transforms`` with the step descriptors of the reference's AffineTransformer (``transforms.py``): the matrices
+it returns warp the images here and their annotations in ``accvlab.draw_heatmap.camera_augment_boxes``."""
 from .prepare import (CHANNEL_PERMUTATIONS, IDENTITY_PHOTOMETRIC, MAX_EXTENT, TILE_H, TILE_W, output_size_transform,
                       padded_hw, prepare_images, sample_photometric_params, sample_positions)
 
-__all__ = ["prepare_images", "sample_photometric_params", "output_size_transform", "padded_hw", "sample_positions",
+from .transforms import (NonUniformScaling, Rotation, Selection, Shearing, ShiftInsideOriginalImage,
+                         ShiftToAlignWithOriginalImageBorder, Translation, UniformScaling, sample_image_transforms)
+
+__all__ = ["sample_image_transforms", "Translation", "ShiftInsideOriginalImage", "ShiftToAlignWithOriginalImageBorder",
+           "Rotation", "UniformScaling", "NonUniformScaling", "Shearing", "Selection",
+           "prepare_images", "sample_photometric_params", "output_size_transform", "padded_hw", "sample_positions",
            "CHANNEL_PERMUTATIONS", "IDENTITY_PHOTOMETRIC", "MAX_EXTENT", "TILE_W", "TILE_H"]

@@ -543,6 +543,72 @@ int accv_visible_boxes_host(const float* boxes, const float* depths, const void*
                             unsigned flags, long long B, long long G, const accv_visible_boxes_params* params,
                             unsigned char* out);
 
+/* -------------------------------------------------------------------------------------------- camera-box augmentation
+ * The annotation side of the reference's camera pipeline for a ragged batch in ONE launch: what AffineTransformer does to
+ * its point fields and projection matrices with the 2 x 3 matrix that warps the image (processing_steps/
+ * affine_transformer.py), then VisibleBboxSelector, the condition "categories >= 0 and is_visible", the
+ * ConditionalElementRemover over bboxes, centers, depths and categories, and the two CoordinateCroppers; wired at
+ * examples/pipeline_setup/stream_petr_pipeline.py (pre_processing_steps).  A frame is one camera image.
+ *
+ * boxes: f32 [F, G, 4] contiguous, rows (x1, y1, x2, y2), corners in either order; transforms: f32 [F, 2, 3], the forward
+ * matrix [[a, b, tx], [c, d, ty]] accv_prepare_images takes; centers: null or f32 [F, G, 2]; depths: null or f32 [F, G],
+ * needed with check_occlusion; categories: null or [F, G] int32 (int64 with ACCV_CB_CATEGORIES_I64); valid: null or bool
+ * bytes [F, G]; counts [F] int32 (int64 with ACCV_CB_COUNTS_I64), clamped to [0, G]: only slots below it are read.  The
+ * image extent is params->image_h x image_w for every frame or, with params->image_hw, rows (H, W) of an [F, 2] int32
+ * (int64 with ACCV_CB_HW_I64) tensor read where the boxes are; either way clamped to [0, 2^24].  Per frame, in float32 (the
+ * operation sequence is written out in csrc/camera_boxes_arith.h, nothing contracted):
+ *   warp        every corner and the centre become ((a*x + b*y) + tx, (c*x + d*y) + ty); with order_corners the box is
+ *               rewritten as (min_x, min_y, max_x, max_y) by the `<` selection of the visible-box selection
+ *   matrices    params->mat_in[i]: f32 [F, mat_count[i], mat_rows[i], mat_cols[i]] with 3 or 4 rows and columns; row 0
+ *               becomes (a*m0j + b*m1j) + tx*m2j, row 1 (c*m0j + d*m1j) + ty*m2j, rows 2 and 3 are copied bit for bit, to
+ *               mat_out[i]
+ *   visible     the decision of accv_visible_boxes on the warped boxes before any crop (check_occlusion, check_size with
+ *               minimum_size, shrink_to_int); with neither check every real slot is visible
+ *   keep        visible && category >= 0 (with categories) && valid (with valid); a box that is not kept still occludes
+ *   crop        with params->crop every kept coordinate v becomes v < 0 ? 0 : (v > E ? E : v), E = W for x, H for y
+ * Outputs: out_boxes f32 [F, G, 4], out_centers f32 [F, G, 2], out_depths f32 [F, G], out_categories [F, G] of the
+ * categories' type (each null exactly when its input is null), source int32 [F, G]: the kept slots compacted in ascending
+ * slot order, the rest of each row 0 and source -1; keep and visible bool bytes [F, G] over the INPUT slots, 0 from
+ * counts[f] on; out_sizes int64 [F], the kept count.  Every output element is written exactly once; inputs and outputs do
+ * not overlap.  One workgroup per frame, no atomics, no workspace, no host synchronisation, bitwise reproducible and
+ * bit-equal to accv_camera_boxes_host, which runs the same operation sequence serially on host memory.  F == 0, or G == 0
+ * without a matrix element, launches nothing and writes nothing; G == 0 with matrices writes them and out_sizes.  Returns ACCV_EINVAL (null params, negative size, unknown flags,
+ * G > ACCV_CB_MAX_BOXES, more than ACCV_CB_MAX_MATRICES matrix tensors, matrices of other than 3 or 4 rows or columns, null or
+ * misaligned pointers, occlusion without depths, an input without its output or the reverse, more workgroups than a grid
+ * holds) before touching the device, ACCV_ELAUNCH if the launch fails. */
+#define ACCV_CB_MAX_BOXES 256
+#define ACCV_CB_MAX_MATRICES 4
+#define ACCV_CB_COUNTS_I64 1u
+#define ACCV_CB_HW_I64 2u
+#define ACCV_CB_CATEGORIES_I64 4u
+/* the scalar parameters, the image extent and the matrix tensors; host memory, read during the call */
+typedef struct accv_camera_boxes_params {
+    double minimum_size;        /* used with check_size */
+    long long image_h, image_w; /* used when image_hw is null */
+    const void* image_hw;       /* null or [F, 2] where the boxes are */
+    const float* mat_in[ACCV_CB_MAX_MATRICES];
+    float* mat_out[ACCV_CB_MAX_MATRICES];
+    long long mat_count[ACCV_CB_MAX_MATRICES];   /* K, matrices per frame */
+    int mat_rows[ACCV_CB_MAX_MATRICES];          /* 3 or 4 */
+    int mat_cols[ACCV_CB_MAX_MATRICES];          /* 3 or 4 */
+    int num_matrices;
+    int check_occlusion;
+    int check_size;
+    int shrink_to_int;
+    int crop;
+    int order_corners;
+} accv_camera_boxes_params;
+int accv_camera_boxes(const float* boxes, const float* transforms, const float* centers, const float* depths,
+                      const void* categories, const unsigned char* valid, const void* counts, unsigned flags, long long F,
+                      long long G, const accv_camera_boxes_params* params, float* out_boxes, float* out_centers,
+                      float* out_depths, void* out_categories, int* source, unsigned char* keep, unsigned char* visible,
+                      long long* out_sizes, void* stream);
+int accv_camera_boxes_host(const float* boxes, const float* transforms, const float* centers, const float* depths,
+                           const void* categories, const unsigned char* valid, const void* counts, unsigned flags,
+                           long long F, long long G, const accv_camera_boxes_params* params, float* out_boxes,
+                           float* out_centers, float* out_depths, void* out_categories, int* source, unsigned char* keep,
+                           unsigned char* visible, long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------- box-to-heat-map targets
  * The step after the visible-box selection: the reference's BoundingBoxToHeatmapConverter
  * (packages/dali_pipeline_framework/.../processing_steps/bounding_box_to_heatmap_converter.py; its helpers
