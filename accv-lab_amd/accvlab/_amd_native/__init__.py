@@ -224,6 +224,12 @@ SIGNATURES = {
     # camera-image preparation (params: a PrepareImagesParams by address; the host entry also takes the coords output)
     "accv_prepare_images": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_prepare_images_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # NV12 surfaces: the conversion (params: an Nv12Params by address) and prepare_images reading the planes (params: a
+    # PrepareImagesNv12Params by address)
+    "accv_nv12_to_rgb": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "accv_nv12_to_rgb_host": (_i, [_vp, _vp, _vp, _vp]),
+    "accv_prepare_images_nv12": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_prepare_images_nv12_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # centre-point decoding with circle NMS (params: a CenterPointDecodeParams by address; outputs [T, B, M, ...])
     "accv_center_point_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_center_point_decode_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -344,6 +350,19 @@ class PrepareImagesParams(ctypes.Structure):
                 ("dtype", ctypes.c_int), ("source_hw_i64", ctypes.c_int)]
 
 
+class Nv12Params(ctypes.Structure):
+    """accv_nv12_params of include/accv_hip.h"""
+    _fields_ = [("batch", ctypes.c_longlong), ("height", ctypes.c_longlong), ("width", ctypes.c_longlong),
+                ("y_stride_batch", ctypes.c_longlong), ("y_stride_row", ctypes.c_longlong),
+                ("uv_stride_batch", ctypes.c_longlong), ("uv_stride_row", ctypes.c_longlong),
+                ("full_range", ctypes.c_int), ("as_bgr", ctypes.c_int), ("chroma_vu", ctypes.c_int)]
+
+
+class PrepareImagesNv12Params(ctypes.Structure):
+    """accv_prepare_images_nv12_params of include/accv_hip.h"""
+    _fields_ = [("prepare", PrepareImagesParams), ("planes", Nv12Params)]
+
+
 class CenterPointDecodeParams(ctypes.Structure):
     """accv_center_point_decode_params of include/accv_hip.h"""
     _fields_ = [("scores", ctypes.c_void_p * 8), ("indices", ctypes.c_void_p * 8), ("classes", ctypes.c_void_p * 8),
@@ -384,7 +403,7 @@ _BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", 
              "accv_center_point_decode_host",
              "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host",
              "accv_camera_boxes_host",
-             "accv_prepare_images_host"}
+             "accv_prepare_images_host", "accv_nv12_to_rgb_host", "accv_prepare_images_nv12_host"}
 
 
 def _fast_entry(fn, res, args):

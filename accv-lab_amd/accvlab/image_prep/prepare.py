@@ -138,74 +138,79 @@ def sample_photometric_params(num_groups, views_per_group, *, min_max_brightness
     return rows.repeat_interleave(views_per_group, dim=0).contiguous()
 
 
-def _three(name, v):
+def _three(name, v, who=_WHO):
     if _is_number(v):
         v = (v, v, v)
     if not isinstance(v, (list, tuple)) or len(v) != 3 or not all(_is_number(x) and math.isfinite(x) for x in v):
-        raise RuntimeError(f"{_WHO}: {name} must be a finite Python number or three of them, got {v!r}")
+        raise RuntimeError(f"{who}: {name} must be a finite Python number or three of them, got {v!r}")
     return tuple(float(x) for x in v)
 
 
 def _prepare(images, output_hw, transforms, source_hw, photometric, is_bgr, mean, std, tile_hw, pad_before_normalize, layout,
-             dtype, out, coords):
-    if not isinstance(images, torch.Tensor):
-        raise RuntimeError(f"{_WHO}: images must be a tensor")
-    if images.dtype != torch.uint8:
-        raise TypeError(f"{_WHO}: images must be uint8 (a decoder's output), got {images.dtype}")
-    if images.dim() != 4 or images.shape[3] != 3:
-        raise RuntimeError(f"{_WHO}: images must be uint8 [B, H, W, 3], got {tuple(images.shape)}")
-    dev = images.device
-    if dev.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: images must be CUDA or CPU tensors, got {dev}")
-    B, Hs, Ws = (int(v) for v in images.shape[:3])
+             dtype, out, coords, who=_WHO, planes=None):
+    """``planes``: None, or the checked NV12 source of ``nv12._planes`` in place of ``images``"""
+    if planes is not None:
+        dev, (B, Hs, Ws), theirs = planes.device, planes.bhw, "planes'"
+    else:
+        if not isinstance(images, torch.Tensor):
+            raise RuntimeError(f"{who}: images must be a tensor")
+        if images.dtype != torch.uint8:
+            raise TypeError(f"{who}: images must be uint8 (a decoder's output), got {images.dtype}")
+        if images.dim() != 4 or images.shape[3] != 3:
+            raise RuntimeError(f"{who}: images must be uint8 [B, H, W, 3], got {tuple(images.shape)}")
+        dev, theirs = images.device, "images'"
+        if dev.type not in ("cuda", "cpu"):
+            raise RuntimeError(f"{who}: images must be CUDA or CPU tensors, got {dev}")
+        B, Hs, Ws = (int(v) for v in images.shape[:3])
     if transforms is None:
-        if output_hw is not None and _hw("output_hw", output_hw) != (Hs, Ws):
-            raise RuntimeError(f"{_WHO}: output_hw {tuple(output_hw)!r} differs from the source's {(Hs, Ws)!r}: that needs transforms")
+        if output_hw is not None and _hw("output_hw", output_hw, who) != (Hs, Ws):
+            raise RuntimeError(f"{who}: output_hw {tuple(output_hw)!r} differs from the source's {(Hs, Ws)!r}: that needs transforms")
         Ho, Wo = Hs, Ws
     else:
-        Ho, Wo = (Hs, Ws) if output_hw is None else _hw("output_hw", output_hw)
+        Ho, Wo = (Hs, Ws) if output_hw is None else _hw("output_hw", output_hw, who)
     if not all(1 <= v <= MAX_EXTENT for v in (Hs, Ws, Ho, Wo)):
-        raise RuntimeError(f"{_WHO}: source {Hs} x {Ws} and output {Ho} x {Wo}: every extent must be in [1, {MAX_EXTENT}]")
-    th, tw = _tile(tile_hw)
-    mean3, std3 = _three("mean", mean), _three("std", std)
+        raise RuntimeError(f"{who}: source {Hs} x {Ws} and output {Ho} x {Wo}: every extent must be in [1, {MAX_EXTENT}]")
+    th, tw = _tile(tile_hw, who)
+    mean3, std3 = _three("mean", mean, who), _three("std", std, who)
     if not all(s > 0 for s in std3):
-        raise ValueError(f"{_WHO}: std must be positive, got {std!r}")
+        raise ValueError(f"{who}: std must be positive, got {std!r}")
     if layout not in _LAYOUTS:
-        raise RuntimeError(f"{_WHO}: layout must be 'CHW' or 'HWC', got {layout!r}")
+        raise RuntimeError(f"{who}: layout must be 'CHW' or 'HWC', got {layout!r}")
     if dtype not in _DTYPES:
-        raise TypeError(f"{_WHO}: dtype must be torch.float32, float16 or bfloat16, got {dtype!r}")
+        raise TypeError(f"{who}: dtype must be torch.float32, float16 or bfloat16, got {dtype!r}")
     for name, t, dtypes, shape in (("transforms", transforms, (torch.float32,), (B, 2, 3)),
                                    ("photometric", photometric, (torch.float32,), (B, 6)),
                                    ("source_hw", source_hw, (torch.int32, torch.int64), (B, 2))):
         if t is None:
             continue
         if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: {name} must be a tensor")
+            raise RuntimeError(f"{who}: {name} must be a tensor")
         if t.is_floating_point() and torch.float32 in dtypes and t.dtype != torch.float32:
-            raise TypeError(f"{_WHO}: {name} must be float32, got {t.dtype}")
+            raise TypeError(f"{who}: {name} must be float32, got {t.dtype}")
         if t.dtype not in dtypes or tuple(t.shape) != shape:
-            raise RuntimeError(f"{_WHO}: {name} must be {' or '.join(str(d) for d in dtypes)} {list(shape)}, "
+            raise RuntimeError(f"{who}: {name} must be {' or '.join(str(d) for d in dtypes)} {list(shape)}, "
                                f"got {t.dtype} {tuple(t.shape)}")
     Hp, Wp = padded_hw((Ho, Wo), (th, tw))
     shape = (B, 3, Hp, Wp) if layout == "CHW" else (B, Hp, Wp, 3)
     if out is not None:
         if not isinstance(out, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: out must be a tensor")
+            raise RuntimeError(f"{who}: out must be a tensor")
         if out.dtype != dtype:
-            raise TypeError(f"{_WHO}: out must be {dtype}, got {out.dtype}")
+            raise TypeError(f"{who}: out must be {dtype}, got {out.dtype}")
         if tuple(out.shape) != shape:
-            raise RuntimeError(f"{_WHO}: out must be {dtype} {list(shape)}, got {tuple(out.shape)}")
+            raise RuntimeError(f"{who}: out must be {dtype} {list(shape)}, got {tuple(out.shape)}")
     for name, t in (("images", images), ("transforms", transforms), ("photometric", photometric), ("source_hw", source_hw),
                     ("out", out)):
         if t is None:
             continue
         if t.device != dev:
-            raise RuntimeError(f"{_WHO}: {name} must be on the images' device {dev}, got {t.device}")
+            raise RuntimeError(f"{who}: {name} must be on the {theirs} device {dev}, got {t.device}")
         if not t.is_contiguous():
-            raise RuntimeError(f"{_WHO}: {name} must be contiguous (it is not copied silently)")
+            raise RuntimeError(f"{who}: {name} must be contiguous (it is not copied silently)")
     result = torch.empty(shape, dtype=dtype, device=dev) if out is None else out
 
-    p = _nat.PrepareImagesParams()
+    full = _nat.PrepareImagesParams() if planes is None else _nat.PrepareImagesNv12Params()
+    p = full if planes is None else full.prepare
     p.batch, p.source_h, p.source_w, p.output_h, p.output_w, p.tile_h, p.tile_w = B, Hs, Ws, Ho, Wo, th, tw
     for c in range(3):
         p.mean[c], p.std[c] = mean3[c], std3[c]
@@ -213,13 +218,22 @@ def _prepare(images, output_hw, transforms, source_hw, photometric, is_bgr, mean
     p.layout, p.dtype = _LAYOUTS[layout], _DTYPES[dtype]
     p.source_hw_i64 = int(source_hw is not None and source_hw.dtype == torch.int64)
     ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731
-    args = (ptr(images), ptr(source_hw), ptr(transforms), ptr(photometric), ctypes.addressof(p), ptr(result))
-    if B > 0:
+    rest = (ptr(source_hw), ptr(transforms), ptr(photometric), ctypes.addressof(full), ptr(result))
+    if B > 0 and planes is not None:
+        planes.fill(full.planes)
+        args = (ptr(planes.y), ptr(planes.uv), *rest)
         if dev.type == "cuda":
             with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_prepare_images(*args, _nat.stream_ptr(dev)), _WHO)
+                _nat.check(_nat.lib().accv_prepare_images_nv12(*args, _nat.stream_ptr(dev)), who)
         else:
-            _nat.check(_nat.lib().accv_prepare_images_host(*args, ptr(coords)), _WHO)
+            _nat.check(_nat.lib().accv_prepare_images_nv12_host(*args), who)
+    elif B > 0:
+        args = (ptr(images), *rest)
+        if dev.type == "cuda":
+            with _nat.device_guard(dev):
+                _nat.check(_nat.lib().accv_prepare_images(*args, _nat.stream_ptr(dev)), who)
+        else:
+            _nat.check(_nat.lib().accv_prepare_images_host(*args, ptr(coords)), who)
     return result
 
 

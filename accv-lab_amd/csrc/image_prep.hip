@@ -17,6 +17,13 @@
 // Every output element is stored exactly once and nothing is read from the output; no clear, no workspace, no atomics, no
 // host synchronisation; bitwise reproducible.  All global indices are 64-bit.
 //
+// The kernel and the host loop are templated on the source kind: Args, the interleaved RGB batch above, or Nv12Args, the two
+// planes of NV12 decoder surfaces addressed by byte strides (accv_prepare_images_nv12).  The NV12 kind converts every source
+// tap to the uint8 triple accv_nv12_to_rgb would have written (nv12_arith.h) and is the same code from there on, so it equals
+// conversion + accv_prepare_images bit for bit; the two taps of a source row share one chroma pair when x0 is even (two
+// adjacent pairs, 4 contiguous bytes, when it is odd), the two rows of a footprint share a chroma row when y0 is even, and
+// without a matrix a lane reads 4 luma bytes and the 4 bytes of its two chroma pairs.  DESIGN.md §9z.
+//
 // One kernel path.  A staged variant for axis-aligned matrices (source rows through LDS) was not built: DESIGN.md §9w has the
 // measurements of what bounds this one.
 #include <hip/hip_runtime.h>
@@ -24,6 +31,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "accv_common.h"
 #include "accv_numeric.h"
@@ -58,12 +66,23 @@ struct Args {
     Norm n;
 };
 
+// the NV12 source kind: `images` is the Y plane, the planes are addressed by byte strides
+struct Nv12Args : Args {
+    const unsigned char* uv;
+    long long y_batch, y_row, uv_batch, uv_row;
+    accv_nv12::Format f;
+};
+
 // everything a pixel of image b needs
 struct Image {
     const unsigned char* px;
     int Wv, Hv;
     Warp w;
     Colour k;
+};
+
+struct Nv12Image : Image {
+    Nv12Source src;
 };
 
 __host__ __device__ inline Image image_of(const Args& a, long long b)
@@ -79,8 +98,32 @@ __host__ __device__ inline Image image_of(const Args& a, long long b)
     return im;
 }
 
+// the same per-image parameters; the planes of image b in place of its pixels
+__host__ __device__ inline Nv12Image image_of(const Nv12Args& a, long long b)
+{
+    Nv12Image im;
+    static_cast<Image&>(im) = image_of(static_cast<const Args&>(a), b);
+    im.px = nullptr;
+    im.src.y = a.images + b * a.y_batch, im.src.uv = a.uv + b * a.uv_batch;
+    im.src.y_pitch = a.y_row, im.src.uv_pitch = a.uv_row;
+    im.src.f = a.f;
+    return im;
+}
+
+// the sampled value of either source kind
+__host__ __device__ inline void sample_source(const Args& a, const Image& im, const Position& p, float (&val)[3])
+{
+    sample(im.px, a.Ws, im.w, p, im.Wv, im.Hv, val);
+}
+
+__host__ __device__ inline void sample_source(const Nv12Args&, const Nv12Image& im, const Position& p, float (&val)[3])
+{
+    sample(im.src, im.w, p, im.Wv, im.Hv, val);
+}
+
 // the three output channels of pixel (X, Y) of the padded output
-__host__ __device__ inline void output_pixel(const Args& a, const Image& im, int X, int Y, float (&o)[3], Position* where)
+template <class A, class I>
+__host__ __device__ inline void output_pixel(const A& a, const I& im, int X, int Y, float (&o)[3], Position* where)
 {
     if (X >= a.Wo || Y >= a.Ho) {
         o[0] = a.n.pad[0], o[1] = a.n.pad[1], o[2] = a.n.pad[2];
@@ -89,7 +132,7 @@ __host__ __device__ inline void output_pixel(const Args& a, const Image& im, int
     const Position p = sample_position(im.w, X, Y, im.Wv, im.Hv);
     if (where) *where = p;
     float val[3];
-    sample(im.px, a.Ws, im.w, p, im.Wv, im.Hv, val);
+    sample_source(a, im, p, val);
     colour_chain(im.k, a.n, val, o);
 }
 
@@ -119,8 +162,9 @@ __device__ __forceinline__ void store_four(void* out, long long off, float v0, f
 }
 
 // ------------------------------------------------------------------------------------------------------------- device
-template <int DT, bool HWC>
-__global__ __launch_bounds__(kThreads) void image_prep_gather_kernel(const Args a)
+// A: the source kind, Args (the interleaved RGB batch) or Nv12Args (the two planes)
+template <int DT, bool HWC, class A>
+__global__ __launch_bounds__(kThreads) void image_prep_gather_kernel(const A a)
 {
     const int tid = threadIdx.x;
     unsigned wg = blockIdx.x;                     // (b * tiles_y + ty) * tiles_x + tx
@@ -131,18 +175,26 @@ __global__ __launch_bounds__(kThreads) void image_prep_gather_kernel(const Args 
     const int Y = ty * kTileH + tid / kLanesPerRow, X = tx * kTileW + (tid % kLanesPerRow) * kLanePixels;
     if (Y >= a.Hp || X >= a.Wp) return;
 
-    const Image im = image_of(a, b);
+    const auto im = image_of(a, b);
     float o[kLanePixels][3];
     if (im.w.copy && Y < im.Hv && X + kLanePixels <= im.Wv) {
-        // without a matrix the lane's four pixels are 12 contiguous source bytes: three 4-byte reads (not aligned)
-        uint32_t w[3];
-        memcpy(w, im.px + ((long long)Y * a.Ws + X) * 3, 12);
+        if constexpr (std::is_same<A, Nv12Args>::value) {
+            // without a matrix the lane's four pixels are 4 luma bytes and the 4 bytes of their two chroma pairs
+            float val[kLanePixels][3];
+            load_four(im.src, X, Y, val);
 #pragma unroll
-        for (int j = 0; j < kLanePixels; ++j) {
-            float val[3];
+            for (int j = 0; j < kLanePixels; ++j) colour_chain(im.k, a.n, val[j], o[j]);
+        } else {
+            // without a matrix the lane's four pixels are 12 contiguous source bytes: three 4-byte reads (not aligned)
+            uint32_t w[3];
+            memcpy(w, im.px + ((long long)Y * a.Ws + X) * 3, 12);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) val[c] = (float)((w[(j * 3 + c) / 4] >> (8 * ((j * 3 + c) % 4))) & 0xffu);
-            colour_chain(im.k, a.n, val, o[j]);
+            for (int j = 0; j < kLanePixels; ++j) {
+                float val[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) val[c] = (float)((w[(j * 3 + c) / 4] >> (8 * ((j * 3 + c) % 4))) & 0xffu);
+                colour_chain(im.k, a.n, val, o[j]);
+            }
         }
     } else {
 #pragma unroll
@@ -179,20 +231,30 @@ __global__ __launch_bounds__(kThreads) void image_prep_gather_kernel(const Args 
     }
 }
 
-template <int DT, bool HWC>
-int launch(const Args& a, hipStream_t stream)
+template <int DT, bool HWC, class A>
+int launch(const A& a, hipStream_t stream)
 {
     const long long groups = a.B * a.tiles_y * a.tiles_x;
-    hipLaunchKernelGGL((image_prep_gather_kernel<DT, HWC>), dim3((unsigned)groups), dim3(kThreads), 0, stream, a);
-    return accv::check_launch("prepare_images");
+    hipLaunchKernelGGL((image_prep_gather_kernel<DT, HWC, A>), dim3((unsigned)groups), dim3(kThreads), 0, stream, a);
+    return accv::check_launch(std::is_same<A, Nv12Args>::value ? "prepare_images_nv12" : "prepare_images");
+}
+
+template <class A>
+int launch_for(const A& a, int dtype, bool hwc, hipStream_t s)
+{
+    switch (dtype) {
+    case kF32: return hwc ? launch<kF32, true>(a, s) : launch<kF32, false>(a, s);
+    case kF16: return hwc ? launch<kF16, true>(a, s) : launch<kF16, false>(a, s);
+    default: return hwc ? launch<kBF16, true>(a, s) : launch<kBF16, false>(a, s);
+    }
 }
 
 // --------------------------------------------------------------------------------------------------------------- host
-template <int DT>
-void host_run(const Args& a, bool hwc)
+template <int DT, class A>
+void host_run(const A& a, bool hwc)
 {
     for (long long b = 0; b < a.B; ++b) {
-        const Image im = image_of(a, b);
+        const auto im = image_of(a, b);
         for (int Y = 0; Y < a.Hp; ++Y)
             for (int X = 0; X < a.Wp; ++X) {
                 float o[3];
@@ -269,6 +331,38 @@ int check_args(const char* who, const unsigned char* images, const void* source_
     return ACCV_OK;
 }
 
+// the NV12 entries: everything the two source kinds share is check_args; the planes' strides and format on top of it
+int check_nv12_args(const char* who, const unsigned char* y, const unsigned char* uv, const void* source_hw,
+                    const float* transforms, const float* photometric, const accv_prepare_images_nv12_params* p, void* out,
+                    Nv12Args& a, int* empty)
+{
+    *empty = 0;
+    if (!p) return accv::fail(ACCV_EINVAL, "%s: null params", who);
+    const accv_nv12_params& pl = p->planes;
+    if (pl.y_stride_batch < 0 || pl.y_stride_row < 0 || pl.uv_stride_batch < 0 || pl.uv_stride_row < 0)
+        return accv::fail(ACCV_EINVAL, "%s: negative stride (y %lld, %lld; uv %lld, %lld)", who, pl.y_stride_batch, pl.y_stride_row,
+                          pl.uv_stride_batch, pl.uv_stride_row);
+    accv_prepare_images_params prepare = p->prepare;
+    prepare.is_bgr = pl.as_bgr;
+    if (int rc = check_args(who, y, source_hw, transforms, photometric, &prepare, out, a, empty)) return rc;
+    if (*empty) return ACCV_OK;
+    if (!uv) return accv::fail(ACCV_EINVAL, "%s: null uv pointer", who);
+    a.uv = uv;
+    a.y_batch = pl.y_stride_batch, a.y_row = pl.y_stride_row, a.uv_batch = pl.uv_stride_batch, a.uv_row = pl.uv_stride_row;
+    a.f.full_range = pl.full_range ? 1 : 0, a.f.as_bgr = pl.as_bgr ? 1 : 0, a.f.vu = pl.chroma_vu ? 1 : 0;
+    return ACCV_OK;
+}
+
+template <class A>
+void host_for(const A& a, int dtype, bool hwc)
+{
+    switch (dtype) {
+    case kF32: host_run<kF32>(a, hwc); break;
+    case kF16: host_run<kF16>(a, hwc); break;
+    default: host_run<kBF16>(a, hwc); break;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,13 +375,7 @@ int accv_prepare_images(const unsigned char* images, const void* source_hw, cons
     int empty;
     if (int rc = check_args(who, images, source_hw, transforms, photometric, params, out, a, &empty)) return rc;
     if (empty) return ACCV_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool hwc = params->layout == ACCV_IP_LAYOUT_HWC;
-    switch (params->dtype) {
-    case kF32: return hwc ? launch<kF32, true>(a, s) : launch<kF32, false>(a, s);
-    case kF16: return hwc ? launch<kF16, true>(a, s) : launch<kF16, false>(a, s);
-    default: return hwc ? launch<kBF16, true>(a, s) : launch<kBF16, false>(a, s);
-    }
+    return launch_for(a, params->dtype, params->layout == ACCV_IP_LAYOUT_HWC, static_cast<hipStream_t>(stream));
 }
 
 int accv_prepare_images_host(const unsigned char* images, const void* source_hw, const float* transforms,
@@ -300,12 +388,31 @@ int accv_prepare_images_host(const unsigned char* images, const void* source_hw,
     if (empty) return ACCV_OK;
     if (reinterpret_cast<uintptr_t>(coords) & 3u) return accv::fail(ACCV_EINVAL, "%s: coords is not aligned to its element size", who);
     a.coords = coords;
-    const bool hwc = params->layout == ACCV_IP_LAYOUT_HWC;
-    switch (params->dtype) {
-    case kF32: host_run<kF32>(a, hwc); break;
-    case kF16: host_run<kF16>(a, hwc); break;
-    default: host_run<kBF16>(a, hwc); break;
-    }
+    host_for(a, params->dtype, params->layout == ACCV_IP_LAYOUT_HWC);
+    return ACCV_OK;
+}
+
+int accv_prepare_images_nv12(const unsigned char* y, const unsigned char* uv, const void* source_hw, const float* transforms,
+                             const float* photometric, const accv_prepare_images_nv12_params* params, void* out, void* stream)
+{
+    const char* who = "prepare_images_nv12";
+    Nv12Args a;
+    int empty;
+    if (int rc = check_nv12_args(who, y, uv, source_hw, transforms, photometric, params, out, a, &empty)) return rc;
+    if (empty) return ACCV_OK;
+    return launch_for(a, params->prepare.dtype, params->prepare.layout == ACCV_IP_LAYOUT_HWC, static_cast<hipStream_t>(stream));
+}
+
+int accv_prepare_images_nv12_host(const unsigned char* y, const unsigned char* uv, const void* source_hw,
+                                  const float* transforms, const float* photometric,
+                                  const accv_prepare_images_nv12_params* params, void* out)
+{
+    const char* who = "prepare_images_nv12 (host)";
+    Nv12Args a;
+    int empty;
+    if (int rc = check_nv12_args(who, y, uv, source_hw, transforms, photometric, params, out, a, &empty)) return rc;
+    if (empty) return ACCV_OK;
+    host_for(a, params->prepare.dtype, params->prepare.layout == ACCV_IP_LAYOUT_HWC);
     return ACCV_OK;
 }
 

@@ -33,6 +33,10 @@
 //              clamp(v) = v < 0 ? 0 : (v > 1 ? 1 : v)
 //   normalise  out[k] = v[k] * scale[k] + bias[k]; scale = 255 / std, bias = -mean / std, float64 rounded once to float32
 //
+// An NV12 source (Nv12Source: the two planes of a decoder surface) has its own load_pixel / load_pair / sample / load_four
+// below: each tap is converted by nv12_arith.h to the uint8 triple the stand-alone conversion writes and handed on as three
+// floats in 0..255, exact, so `sample` and everything after it see what they would see from the converted RGB batch.
+//
 // The longest chain of ROUNDED operations from the four source bytes to an output (every stage active), which the tests'
 // tolerance is built from: ax (1), p00 * ax (1), + p01 * wx (1), top * ay (1), + bot * wy (1), kInv255 and its product (2),
 // delta (1), alpha_pre (1), the hue path sh, div_rn(sh, 6), shift, h + shift, the wrap, 1 - f, s * (1 - f), 1 - (.), mx * (.)
@@ -45,6 +49,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+
+#include "nv12_arith.h"
 
 #pragma clang fp contract(off)
 
@@ -147,6 +153,19 @@ __host__ __device__ inline void load_pair(const unsigned char* img, long long pi
     load_pixel(img, pitch, x + 1, y, Wv, Hv, r);
 }
 
+// the bilinear blend of the four taps, per channel
+__host__ __device__ inline void blend(const float (&p00)[3], const float (&p01)[3], const float (&p10)[3], const float (&p11)[3],
+                                      const Position& p, float (&val)[3])
+{
+    const float ax = 1.0f - p.wx, ay = 1.0f - p.wy;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = p00[c] * ax + p01[c] * p.wx;
+        const float bot = p10[c] * ax + p11[c] * p.wx;
+        val[c] = top * ay + bot * p.wy;
+    }
+}
+
 // the sampled value in 0..255 per channel
 __host__ __device__ inline void sample(const unsigned char* img, long long pitch, const Warp& w, const Position& p, int Wv,
                                        int Hv, float (&val)[3])
@@ -160,12 +179,103 @@ __host__ __device__ inline void sample(const unsigned char* img, long long pitch
     float p00[3], p01[3], p10[3], p11[3];
     load_pair(img, pitch, p.x0, p.y0, Wv, Hv, p00, p01);
     load_pair(img, pitch, p.x0, p.y0 + 1, Wv, Hv, p10, p11);
-    const float ax = 1.0f - p.wx, ay = 1.0f - p.wy;
+    blend(p00, p01, p10, p11, p, val);
+}
+
+// ---- the same three functions for a source of NV12 planes: every tap is converted to the uint8 triple nv12_to_rgb would
+// have written (nv12_arith.h) and handed on as floats, so everything after the load is the code above
+struct Nv12Source {
+    const unsigned char* y;      // luma of the image: pixel (x, y) at y * y_pitch + x
+    const unsigned char* uv;     // chroma of the image: the pair of sample (i, r) at r * uv_pitch + 2 * i
+    long long y_pitch, uv_pitch; // bytes
+    accv_nv12::Format f;
+};
+
+__host__ __device__ inline void nv12_tap(const accv_nv12::Format& f, int Y, int e, int o, float (&out)[3])
+{
+    int c0, c1, c2;
+    accv_nv12::convert(f, Y, e, o, c0, c1, c2);
+    out[0] = (float)c0, out[1] = (float)c1, out[2] = (float)c2;
+}
+
+// 0 outside the valid extent.  The chroma sample (x / 2, y / 2) of a valid pixel always lies in the plane.
+__host__ __device__ inline void load_pixel(const Nv12Source& s, int x, int y, int Wv, int Hv, float (&o)[3])
+{
+    o[0] = o[1] = o[2] = 0.0f;
+    if (x < 0 || y < 0 || x >= Wv || y >= Hv) return;
+    const unsigned char* q = s.uv + (y / 2) * s.uv_pitch + (x / 2) * 2;
+    nv12_tap(s.f, s.y[y * s.y_pitch + x], q[0], q[1], o);
+}
+
+// the chroma pairs of pixels x and x + 1 (both inside the plane's width) of chroma row cy, as (e0, o0, e1, o1) in one word:
+// one UV pair (2 bytes) when x is even, two adjacent ones (4 contiguous bytes) when it is odd.  Not aligned.
+__host__ __device__ inline uint32_t load_chroma_pair(const Nv12Source& s, int x, int cy)
+{
+    const unsigned char* q = s.uv + cy * s.uv_pitch + (x / 2) * 2;
+    if (x & 1) {
+        uint32_t w;
+        memcpy(&w, q, 4);
+        return w;
+    }
+    uint16_t h;
+    memcpy(&h, q, 2);
+    return (uint32_t)h | ((uint32_t)h << 16);
+}
+
+// the two taps (x, y), (x + 1, y), both inside, from their chroma word
+__host__ __device__ inline void nv12_pair(const Nv12Source& s, int x, int y, uint32_t chroma, float (&l)[3], float (&r)[3])
+{
+    uint16_t luma;
+    memcpy(&luma, s.y + y * s.y_pitch + x, 2);
+    nv12_tap(s.f, (int)(luma & 0xffu), (int)(chroma & 0xffu), (int)((chroma >> 8) & 0xffu), l);
+    nv12_tap(s.f, (int)(luma >> 8), (int)((chroma >> 16) & 0xffu), (int)(chroma >> 24), r);
+}
+
+// the two horizontally adjacent taps (x, y) and (x + 1, y): when both lie inside, two luma bytes and their chroma word,
+// else pixel by pixel.  Same values.
+__host__ __device__ inline void load_pair(const Nv12Source& s, int x, int y, int Wv, int Hv, float (&l)[3], float (&r)[3])
+{
+    if (y >= 0 && y < Hv && x >= 0 && x + 1 < Wv) {
+        nv12_pair(s, x, y, load_chroma_pair(s, x, y / 2), l, r);
+        return;
+    }
+    load_pixel(s, x, y, Wv, Hv, l);
+    load_pixel(s, x + 1, y, Wv, Hv, r);
+}
+
+// a footprint that lies inside reads the chroma of its two rows once when y0 is even: they share the chroma row
+__host__ __device__ inline void sample(const Nv12Source& s, const Warp& w, const Position& p, int Wv, int Hv, float (&val)[3])
+{
+    val[0] = val[1] = val[2] = 0.0f;
+    if (!p.inside) return;
+    if (w.copy) {
+        load_pixel(s, p.x0, p.y0, Wv, Hv, val);
+        return;
+    }
+    float p00[3], p01[3], p10[3], p11[3];
+    if (p.y0 >= 0 && p.y0 + 1 < Hv && p.x0 >= 0 && p.x0 + 1 < Wv) {
+        const uint32_t top = load_chroma_pair(s, p.x0, p.y0 / 2);
+        const uint32_t bot = (p.y0 & 1) ? load_chroma_pair(s, p.x0, p.y0 / 2 + 1) : top;
+        nv12_pair(s, p.x0, p.y0, top, p00, p01);
+        nv12_pair(s, p.x0, p.y0 + 1, bot, p10, p11);
+    } else {
+        load_pair(s, p.x0, p.y0, Wv, Hv, p00, p01);
+        load_pair(s, p.x0, p.y0 + 1, Wv, Hv, p10, p11);
+    }
+    blend(p00, p01, p10, p11, p, val);
+}
+
+// without a matrix: the four pixels (X .. X + 3, Y), X a multiple of 4 and all inside, from 4 luma bytes and the 4 chroma
+// bytes of their two pairs (two 4-byte reads, not aligned)
+__host__ __device__ inline void load_four(const Nv12Source& s, int X, int Y, float (&val)[4][3])
+{
+    uint32_t luma, chroma;
+    memcpy(&luma, s.y + Y * s.y_pitch + X, 4);
+    memcpy(&chroma, s.uv + (Y / 2) * s.uv_pitch + X, 4);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float top = p00[c] * ax + p01[c] * p.wx;
-        const float bot = p10[c] * ax + p11[c] * p.wx;
-        val[c] = top * ay + bot * p.wy;
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t pair = chroma >> (16 * (j / 2));
+        nv12_tap(s.f, (int)((luma >> (8 * j)) & 0xffu), (int)(pair & 0xffu), (int)((pair >> 8) & 0xffu), val[j]);
     }
 }
 

@@ -737,6 +737,53 @@ int accv_prepare_images(const unsigned char* images, const void* source_hw, cons
 int accv_prepare_images_host(const unsigned char* images, const void* source_hw, const float* transforms,
                              const float* photometric, const accv_prepare_images_params* params, void* out, float* coords);
 
+/* --------------------------------------------------------------------------------------------------------- NV12 surfaces
+ * What a hardware video or JPEG decoder hands out: a pitched Y plane and an interleaved, 2 x 2 subsampled UV plane.  The
+ * reference converts them in on_demand_video_decoder (convert_nv12_to_rgb, ColorConvertKernels.cu); the per-pixel
+ * arithmetic is written out in csrc/nv12_arith.h: chroma sample (y / 2, x / 2) taken nearest; limited range in int32
+ * fixed point (bit-equal to the reference), full range in float32 with every operator one IEEE operation (the reference's
+ * fast-math build may contract them into fma; this library does not).
+ *
+ * y: u8, pixel (b, r, x) at byte b * y_stride_batch + r * y_stride_row + x.  uv: u8, the pair of chroma sample (b, r, i) at
+ * bytes b * uv_stride_batch + r * uv_stride_row + 2 i and + 1, for r < ceil(height / 2), i < ceil(width / 2); U is the even
+ * byte, or V with chroma_vu (NV21).  Strides are in bytes and not negative; nothing beyond `width` bytes of a Y row and
+ * 2 * ceil(width / 2) bytes of a UV row is read.  as_bgr: the triple is written as B, G, R.
+ *
+ * accv_nv12_to_rgb writes out, u8 [batch, height, width, 3] contiguous, every byte once: a workgroup per (image, 64 x 16
+ * tile), 4 consecutive x per lane (4 Y bytes and 4 chroma bytes in, 12 bytes out as three 4-byte stores when the address is
+ * aligned, per byte otherwise); no workspace, no atomics, no host synchronisation.  batch == 0 launches nothing.  Returns
+ * ACCV_EINVAL (null params, negative batch or stride, an extent outside [1, ACCV_IP_MAX_EXTENT], null pointers, more
+ * workgroups than a grid holds) before touching the device, ACCV_ELAUNCH if the launch fails.  accv_nv12_to_rgb_host runs
+ * the same operation sequence serially on host memory and is bit-equal. */
+typedef struct accv_nv12_params {
+    long long batch, height, width;
+    long long y_stride_batch, y_stride_row;       /* bytes */
+    long long uv_stride_batch, uv_stride_row;     /* bytes */
+    int full_range;
+    int as_bgr;
+    int chroma_vu;
+} accv_nv12_params;
+int accv_nv12_to_rgb(const unsigned char* y, const unsigned char* uv, const accv_nv12_params* params, unsigned char* out,
+                     void* stream);
+int accv_nv12_to_rgb_host(const unsigned char* y, const unsigned char* uv, const accv_nv12_params* params, unsigned char* out);
+
+/* accv_prepare_images reading NV12 planes instead of an RGB batch: every source tap is converted to the uint8 triple that
+ * accv_nv12_to_rgb would have written, and the rest is accv_prepare_images unchanged, so the result is bit-equal to
+ * accv_nv12_to_rgb followed by accv_prepare_images with is_bgr = as_bgr.  prepare: as for accv_prepare_images (source_h,
+ * source_w are the planes' luma extent; its is_bgr is ignored, planes->as_bgr takes its place).  planes: the strides and the
+ * format (its batch, height and width are ignored).  source_hw: the valid region inside the planes; luma outside it is never
+ * read, and the chroma sample of a valid pixel always lies in the plane.  Same launch shape, checks and status codes as
+ * accv_prepare_images, and ACCV_EINVAL also for a null uv pointer or a negative stride. */
+typedef struct accv_prepare_images_nv12_params {
+    accv_prepare_images_params prepare;
+    accv_nv12_params planes;
+} accv_prepare_images_nv12_params;
+int accv_prepare_images_nv12(const unsigned char* y, const unsigned char* uv, const void* source_hw, const float* transforms,
+                             const float* photometric, const accv_prepare_images_nv12_params* params, void* out, void* stream);
+int accv_prepare_images_nv12_host(const unsigned char* y, const unsigned char* uv, const void* source_hw,
+                                  const float* transforms, const float* photometric,
+                                  const accv_prepare_images_nv12_params* params, void* out);
+
 /* ------------------------------------------------------------------------------------------------ centre-point decoding
  * The prediction side of a centre-point head, the inverse of accv_center_point_targets: mmdet3d's
  * CenterPointBBoxCoder.decode (core/bbox/coders/centerpoint_bbox_coders.py: the gathers, exp, atan2, the affine map back
