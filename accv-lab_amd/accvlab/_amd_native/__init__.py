@@ -395,15 +395,8 @@ if os.environ.get("ACCV_NO_FASTCALL") == "1":
 _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 # entry points that BLOCK (wait for a native job, run a long host memcpy): they stay on ctypes, which drops the
 # interpreter lock for the duration of the call — the trampoline keeps it
-_BLOCKING = {"accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
-             "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
-             "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
-             "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
-             "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_bev_augment_host",
-             "accv_center_point_decode_host",
-             "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host", "accv_visible_boxes_host", "accv_box_heatmap_host",
-             "accv_camera_boxes_host",
-             "accv_prepare_images_host", "accv_nv12_to_rgb_host", "accv_prepare_images_nv12_host"}
+# every host entry runs its whole operator inside the call
+_BLOCKING = {name for name in SIGNATURES if name.endswith("_host")} | {"accv_mtc_async_wait", "accv_mtc_stage_h2d"}
 
 
 def _fast_entry(fn, res, args):

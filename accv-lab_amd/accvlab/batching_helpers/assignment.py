@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
 from .data_format import RaggedBatch
 
 __all__ = ["batched_linear_sum_assignment"]
@@ -107,16 +108,12 @@ def batched_linear_sum_assignment(cost, *, maximize: bool = False, check: bool =
                 row_counts.data_ptr() if row_counts is not None else 0,
                 col_counts.data_ptr() if col_counts is not None else 0, flags,
                 row.data_ptr(), col.data_ptr(), sizes.data_ptr(), status.data_ptr())
-        lib = _nat.lib()
-        if x.is_cuda:
-            ws = _nat.workspace(lib.accv_linear_assignment_workspace_bytes(B, R, C, _DTYPES[x.dtype]), dev)
-            with _nat.device_guard(dev):
-                _nat.check(lib.accv_linear_assignment(*args, ws.data_ptr(), ws.numel(), _nat.stream_ptr(dev)),
-                           "batched_linear_sum_assignment")
-        elif dev.type == "cpu":
-            _nat.check(lib.accv_linear_assignment_host(*args), "batched_linear_sum_assignment")
-        else:
+        if x.is_cuda:   # the device entry takes a workspace behind the host entry's arguments
+            ws = _nat.workspace(_nat.lib().accv_linear_assignment_workspace_bytes(B, R, C, _DTYPES[x.dtype]), dev)
+            args += (ws.data_ptr(), ws.numel())
+        elif dev.type != "cpu":
             raise RuntimeError(f"batched_linear_sum_assignment: unsupported device {dev}")
+        _ops.run("accv_linear_assignment", args, dev, "batched_linear_sum_assignment")
 
     if check:
         st = status.cpu()

@@ -14,6 +14,7 @@ import struct
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
 from .assignment import batched_linear_sum_assignment
 from .ragged import RaggedBatch
 
@@ -180,14 +181,9 @@ def batched_matching_cost(pred_scores, gt_labels, pred_boxes=None, gt_boxes=None
                 scores.stride(0) if use_cls else 0, scores.stride(1) if use_cls else 0,
                 pboxes.stride(0) if use_box else 0, pboxes.stride(1) if use_box else 0,
                 ctypes.addressof(p), out.data_ptr())
-        lib = _nat.lib()
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(lib.accv_matching_cost(*args, _nat.stream_ptr(dev)), "batched_matching_cost")
-        elif dev.type == "cpu":
-            _nat.check(lib.accv_matching_cost_host(*args), "batched_matching_cost")
-        else:
+        if dev.type not in ("cuda", "cpu"):
             raise RuntimeError(f"batched_matching_cost: unsupported device {dev}")
+        _ops.run("accv_matching_cost", args, dev, "batched_matching_cost")
     return sizes_rb.create_with_sample_sizes_like_self(out, non_uniform_dim=2)
 
 

@@ -17,6 +17,8 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 MAX_POINT_TRANSFORMS = _nat.BA_MAX_POINT_TRANSFORMS
 MAX_FRAME_TRANSFORMS = _nat.BA_MAX_FRAME_TRANSFORMS
@@ -32,10 +34,6 @@ class BevAugmented(NamedTuple):
     keep: object                # RaggedBatch bool [B, Nmax] over the INPUT slots
     point_transforms: tuple     # new tensors, M . A^-1
     frame_transforms: tuple     # new tensors, A . M
-
-
-def _is_ragged(x) -> bool:
-    return hasattr(x, "tensor") and hasattr(x, "sample_sizes")
 
 
 def _column(name, v, B, device, who):
@@ -218,25 +216,14 @@ def bev_augment_boxes(boxes, params: torch.Tensor, *, labels=None, valid=None, p
     synchronisation, bitwise reproducible); CPU tensors run the library's serial host entry over the same arithmetic, with
     bit-equal results.  Nothing takes a gradient and no input is modified.  ``B == 0`` gives empty outputs without a launch.
     """
-    from ..batching_helpers import RaggedBatch
-
-    if not _is_ragged(boxes):
+    if not _ops.is_ragged(boxes):
         raise RuntimeError(f"{_WHO}: boxes must be a RaggedBatch of float32 [B, Nmax, D]")
     b_t, sizes = boxes.tensor, boxes.sample_sizes
-    l_t = labels.tensor if _is_ragged(labels) else labels
-    v_t = valid.tensor if _is_ragged(valid) else valid
-    for name, t in (("boxes", b_t), ("params", params), ("labels", l_t), ("valid", v_t), ("sample_sizes", sizes)):
-        if t is None and name in ("labels", "valid"):
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: {name} must be a tensor")
-        if t.device != b_t.device:
-            raise RuntimeError(f"{_WHO}: {name} must be on the boxes' device {b_t.device}, got {t.device}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{_WHO}: {name} must be contiguous (it is not copied silently)")
+    l_t, v_t = _ops.tensor_of(labels), _ops.tensor_of(valid)
+    _ops.check_operands(_WHO, (("boxes", b_t), ("params", params), ("labels", l_t), ("valid", v_t), ("sample_sizes", sizes)),
+                        b_t, "boxes'", required=("boxes", "params", "sample_sizes"))
     dev = b_t.device
-    if dev.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: boxes must be CUDA or CPU tensors, got {dev}")
+    _ops.check_backend(_WHO, "boxes", dev)
     if b_t.dtype != torch.float32 or b_t.dim() != 3 or b_t.shape[2] not in (7, 9):
         raise RuntimeError(f"{_WHO}: boxes must be float32 [B, Nmax, 7 or 9], got {b_t.dtype} {tuple(b_t.shape)}")
     B, N, D = b_t.shape
@@ -246,8 +233,7 @@ def bev_augment_boxes(boxes, params: torch.Tensor, *, labels=None, valid=None, p
         raise RuntimeError(f"{_WHO}: labels must be int32 or int64 [{B}, {N}], got {l_t.dtype} {tuple(l_t.shape)}")
     if v_t is not None and (v_t.dtype not in (torch.bool, torch.uint8) or tuple(v_t.shape) != (B, N)):
         raise RuntimeError(f"{_WHO}: valid must be bool or uint8 [{B}, {N}], got {v_t.dtype} {tuple(v_t.shape)}")
-    if sizes.dtype not in (torch.int32, torch.int64) or tuple(sizes.shape) != (B,):
-        raise RuntimeError(f"{_WHO}: sample_sizes must be int32 or int64 [{B}], got {sizes.dtype} {tuple(sizes.shape)}")
+    _ops.check_sample_sizes(_WHO, sizes, B)
     if range_check_on not in ("input", "output"):
         raise RuntimeError(f"{_WHO}: range_check_on must be 'input' or 'output', got {range_check_on!r}")
     rng = _range(point_range)
@@ -275,15 +261,10 @@ def bev_augment_boxes(boxes, params: torch.Tensor, *, labels=None, valid=None, p
         flags = ((_nat.BA_LABELS_I64 if l_t is not None and l_t.dtype == torch.int64 else 0)
                  | (_nat.BA_COUNTS_I64 if sizes.dtype == torch.int64 else 0)
                  | (_nat.BA_RANGE_ON_OUTPUT if range_check_on == "output" else 0))
-        args = (b_t.data_ptr(), params.data_ptr(), l_t.data_ptr() if l_t is not None else None,
-                v_t.data_ptr() if v_t is not None else None, sizes.data_ptr(), flags, B, N, D, ctypes.addressof(prm),
-                out_boxes.data_ptr(), out_labels.data_ptr() if out_labels is not None else None, source.data_ptr(),
-                keep.data_ptr(), kept.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_bev_augment(*args, _nat.stream_ptr(dev)), _WHO)
-        else:
-            _nat.check(_nat.lib().accv_bev_augment_host(*args), _WHO)
+        args = (b_t.data_ptr(), params.data_ptr(), _ops.ptr(l_t), _ops.ptr(v_t), sizes.data_ptr(), flags, B, N, D,
+                ctypes.addressof(prm), out_boxes.data_ptr(), _ops.ptr(out_labels), source.data_ptr(), keep.data_ptr(),
+                kept.data_ptr())
+        _ops.run("accv_bev_augment", args, dev, _WHO)
     return BevAugmented(RaggedBatch(out_boxes, sample_sizes=kept),
                         RaggedBatch(out_labels, sample_sizes=kept) if out_labels is not None else None,
                         RaggedBatch(source, sample_sizes=kept), RaggedBatch(keep, sample_sizes=sizes), p_out, f_out)

@@ -18,6 +18,8 @@ from typing import NamedTuple
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 MAX_BOXES = _nat.BH_MAX_BOXES
 MAX_CATEGORIES = _nat.BH_MAX_CATEGORIES
@@ -35,16 +37,8 @@ class BoxHeatmapTargets(NamedTuple):
     radii: object                  # float32 [B, G]
 
 
-def _is_ragged(x) -> bool:
-    return hasattr(x, "tensor") and hasattr(x, "sample_sizes")
-
-
-def _is_number(v) -> bool:
-    return isinstance(v, (int, float)) and not isinstance(v, bool)
-
-
 def _pair(name, v):
-    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_is_number(x) for x in v):
+    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_ops.is_number(x) for x in v):
         raise RuntimeError(f"{_WHO}: {name} must be a (height, width) pair of Python numbers, got {v!r}")
     return float(v[0]), float(v[1])
 
@@ -117,9 +111,7 @@ def boxes_to_heatmap(bboxes, *, image_hw, heatmap_hw, centers=None, categories=N
     tile; every workgroup recomputes its frame's records, so there is no pre-pass, no workspace, no atomics and no host
     synchronisation); CPU tensors run the library's host entry over the same per-object functions.  Nothing takes a gradient.
     """
-    from ..batching_helpers import RaggedBatch
-
-    if not _is_ragged(bboxes):
+    if not _ops.is_ragged(bboxes):
         raise RuntimeError(f"{_WHO}: bboxes must be a RaggedBatch of float32 [B, G_max, 4]")
     b_t, sizes = bboxes.tensor, bboxes.sample_sizes
 
@@ -145,14 +137,14 @@ def boxes_to_heatmap(bboxes, *, image_hw, heatmap_hw, centers=None, categories=N
         cat_sizes = [_pair("an entry of per_category_min_object_sizes", v) for v in per_category_min_object_sizes]
     glob_size = _pair("min_object_size", min_object_size) if min_object_size is not None else (0.0, 0.0)
     if (not isinstance(heatmap_hw, (list, tuple)) or len(heatmap_hw) != 2
-            or any(isinstance(v, bool) or not isinstance(v, int) for v in heatmap_hw)
+            or not all(_ops.is_int(v) for v in heatmap_hw)
             or not all(1 <= v <= (1 << 24) for v in heatmap_hw)):
         raise RuntimeError(f"{_WHO}: heatmap_hw must be (H, W) Python ints in [1, 2^24], got {heatmap_hw!r}")
     Hm, Wm = heatmap_hw
     scalars = dict(min_fraction_area_clipping=min_fraction_area_clipping, min_radius=min_radius, max_radius=max_radius,
                    radius_scaling_factor=radius_scaling_factor, radius_to_sigma_factor=radius_to_sigma_factor)
     for name, v in scalars.items():
-        if not _is_number(v) or not math.isfinite(v):
+        if not _ops.is_number(v) or not math.isfinite(v):
             raise RuntimeError(f"{_WHO}: {name} must be a finite Python number, got {v!r}")
     if not 0 < max_radius <= 16384:
         raise RuntimeError(f"{_WHO}: max_radius must be in (0, 16384], got {max_radius!r}")
@@ -161,55 +153,28 @@ def boxes_to_heatmap(bboxes, *, image_hw, heatmap_hw, centers=None, categories=N
     planes = num_categories if use_per_category_heatmap else 1
     if k_for_classes is not None:
         if (not isinstance(k_for_classes, (list, tuple)) or len(k_for_classes) != planes
-                or not all(_is_number(v) and math.isfinite(v) for v in k_for_classes)):
+                or not all(_ops.is_number(v) and math.isfinite(v) for v in k_for_classes)):
             raise RuntimeError(f"{_WHO}: k_for_classes must hold {planes} finite Python numbers (one per plane), "
                                f"got {k_for_classes!r}")
 
-    c_t = None if centers is None else (centers.tensor if _is_ragged(centers) else centers)
-    cat_t = None if categories is None else (categories.tensor if _is_ragged(categories) else categories)
-    v_t = None if is_valid is None else (is_valid.tensor if _is_ragged(is_valid) else is_valid)
+    c_t, cat_t, v_t = _ops.tensor_of(centers), _ops.tensor_of(categories), _ops.tensor_of(is_valid)
     hw_t = image_hw if isinstance(image_hw, torch.Tensor) else None
-    for name, t in (("bboxes", b_t), ("centers", c_t), ("categories", cat_t), ("is_valid", v_t), ("sample_sizes", sizes),
-                    ("image_hw", hw_t), ("out", out)):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: {name} must be a tensor")
-        if t.device != b_t.device:
-            raise RuntimeError(f"{_WHO}: {name} must be on the boxes' device {b_t.device}, got {t.device}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{_WHO}: {name} must be contiguous (it is not copied silently)")
-    if b_t.device.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: bboxes must be CUDA or CPU tensors, got {b_t.device}")
-    if b_t.is_floating_point() and b_t.dtype != torch.float32:
-        raise TypeError(f"{_WHO}: bboxes must be float32 (the definition is float32), got {b_t.dtype}")
-    if (b_t.dtype != torch.float32 or b_t.dim() != 3 or b_t.shape[2] != 4 or getattr(bboxes, "num_batch_dims", 1) != 1
-            or getattr(bboxes, "non_uniform_dim", 1) != 1):
-        raise RuntimeError(f"{_WHO}: bboxes must be float32 [B, G_max, 4] with one batch dimension and non_uniform_dim 1, "
-                           f"got {b_t.dtype} {tuple(b_t.shape)}")
-    B, G = int(b_t.shape[0]), int(b_t.shape[1])
+    _ops.check_operands(_WHO, (("bboxes", b_t), ("centers", c_t), ("categories", cat_t), ("is_valid", v_t),
+                               ("sample_sizes", sizes), ("image_hw", hw_t), ("out", out)), b_t, "boxes'")
+    _ops.check_backend(_WHO, "bboxes", b_t.device)
+    _ops.check_float32(_WHO, "bboxes", b_t)
+    B, G = _ops.check_bboxes(_WHO, bboxes, b_t, "[B, G_max, 4]")
     if c_t is not None:
-        if c_t.is_floating_point() and c_t.dtype != torch.float32:
-            raise TypeError(f"{_WHO}: centers must be float32 (the definition is float32), got {c_t.dtype}")
+        _ops.check_float32(_WHO, "centers", c_t)
         if c_t.dtype != torch.float32 or tuple(c_t.shape) != (B, G, 2):
             raise RuntimeError(f"{_WHO}: centers must be float32 [{B}, {G}, 2], got {c_t.dtype} {tuple(c_t.shape)}")
     if cat_t is not None and (cat_t.dtype not in (torch.int32, torch.int64) or tuple(cat_t.shape) != (B, G)):
         raise RuntimeError(f"{_WHO}: categories must be int32 or int64 [{B}, {G}], got {cat_t.dtype} {tuple(cat_t.shape)}")
     if v_t is not None and (v_t.dtype != torch.bool or tuple(v_t.shape) != (B, G)):
         raise RuntimeError(f"{_WHO}: is_valid must be bool [{B}, {G}], got {v_t.dtype} {tuple(v_t.shape)}")
-    if sizes.dtype not in (torch.int32, torch.int64) or tuple(sizes.shape) != (B,):
-        raise RuntimeError(f"{_WHO}: sample_sizes must be int32 or int64 [{B}], got {sizes.dtype} {tuple(sizes.shape)}")
-    Hi = Wi = 0
-    if hw_t is not None:
-        if hw_t.dtype not in (torch.int32, torch.int64) or tuple(hw_t.shape) != (B, 2):
-            raise RuntimeError(f"{_WHO}: an image_hw tensor must be int32 or int64 [{B}, 2], got {hw_t.dtype} {tuple(hw_t.shape)}")
-    else:
-        if (not isinstance(image_hw, (list, tuple)) or len(image_hw) != 2
-                or any(isinstance(v, bool) or not isinstance(v, int) for v in image_hw)):
-            raise RuntimeError(f"{_WHO}: image_hw must be (H, W) Python ints or an integer tensor [B, 2], got {image_hw!r}")
-        Hi, Wi = (max(0, min(int(v), 1 << 24)) for v in image_hw)
-    if G > MAX_BOXES:
-        raise RuntimeError(f"{_WHO}: {G} box slots per frame, at most MAX_BOXES = {MAX_BOXES} are supported")
+    _ops.check_sample_sizes(_WHO, sizes, B)
+    Hi, Wi = _ops.image_hw_args(_WHO, image_hw, hw_t, B, "B")
+    _ops.check_box_count(_WHO, G, MAX_BOXES)
     map_shape = (B, planes, Hm, Wm) if use_per_category_heatmap else (B, Hm, Wm)
     dev = b_t.device
     if out is not None:
@@ -247,14 +212,10 @@ def boxes_to_heatmap(bboxes, *, image_hw, heatmap_hw, centers=None, categories=N
         flags = ((_nat.BH_COUNTS_I64 if sizes.dtype == torch.int64 else 0)
                  | (_nat.BH_HW_I64 if hw_t is not None and hw_t.dtype == torch.int64 else 0)
                  | (_nat.BH_CATEGORIES_I64 if cat_t is not None and cat_t.dtype == torch.int64 else 0))
-        ptr = lambda t: None if t is None else t.data_ptr()
+        ptr = _ops.ptr
         args = (ptr(b_t), ptr(c_t), ptr(cat_t), ptr(v_t), ptr(sizes), ptr(hw_t), flags, B, G, ctypes.addressof(params),
                 ptr(heatmap), ptr(active), ptr(center), ptr(offset), ptr(hw_out), ptr(boxes_out), ptr(radii))
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_box_heatmap(*args, _nat.stream_ptr(dev)), _WHO)
-        else:
-            _nat.check(_nat.lib().accv_box_heatmap_host(*args), _WHO)
+        _ops.run("accv_box_heatmap", args, dev, _WHO)
     ragged = lambda t: RaggedBatch(t, sample_sizes=sizes)
     return BoxHeatmapTargets(heatmap, ragged(active), ragged(center), ragged(offset), ragged(hw_out), ragged(boxes_out),
                              ragged(radii))

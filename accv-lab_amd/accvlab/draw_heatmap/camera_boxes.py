@@ -17,6 +17,8 @@ from typing import NamedTuple, Sequence
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 MAX_BOXES = _nat.CB_MAX_BOXES
 MAX_MATRICES = _nat.CB_MAX_MATRICES
@@ -34,10 +36,6 @@ class CameraBoxes(NamedTuple):
     keep: object                    # RaggedBatch bool [F, G] over the INPUT slots
     visible: object                 # RaggedBatch bool [F, G] over the INPUT slots
     projection_matrices: tuple      # new tensors, [[A], [0 0 1]] . M
-
-
-def _is_ragged(x) -> bool:
-    return hasattr(x, "tensor") and hasattr(x, "sample_sizes")
 
 
 def _matrices(tensors, F, device):
@@ -115,41 +113,25 @@ def camera_augment_boxes(bboxes, transforms: torch.Tensor, *, image_hw, centers=
     bit-equal results.  Nothing takes a gradient and no input is modified.  ``F == 0`` or ``G == 0`` gives empty
     compacted outputs without a launch (with ``G == 0`` the projection matrices, if any, still take one).
     """
-    from ..batching_helpers import RaggedBatch
-
-    if not _is_ragged(bboxes):
+    if not _ops.is_ragged(bboxes):
         raise RuntimeError(f"{_WHO}: bboxes must be a RaggedBatch of float32 [F, G, 4]")
     b_t, sizes = bboxes.tensor, bboxes.sample_sizes
     if check_occlusion and depths is None:
         raise RuntimeError(f"{_WHO}: check_occlusion needs depths")
-    c_t = centers.tensor if _is_ragged(centers) else centers
-    d_t = depths.tensor if _is_ragged(depths) else depths
-    k_t = categories.tensor if _is_ragged(categories) else categories
-    v_t = valid.tensor if _is_ragged(valid) else valid
+    c_t, d_t = _ops.tensor_of(centers), _ops.tensor_of(depths)
+    k_t, v_t = _ops.tensor_of(categories), _ops.tensor_of(valid)
     hw_t = image_hw if isinstance(image_hw, torch.Tensor) else None
     if not isinstance(b_t, torch.Tensor):
         raise RuntimeError(f"{_WHO}: bboxes must be a RaggedBatch of float32 [F, G, 4]")
-    for name, t in (("bboxes", b_t), ("transforms", transforms), ("centers", c_t), ("depths", d_t), ("categories", k_t),
-                    ("valid", v_t), ("sample_sizes", sizes), ("image_hw", hw_t)):
-        if t is None and name not in ("bboxes", "transforms", "sample_sizes"):
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: {name} must be a tensor")
-        if t.device != b_t.device:
-            raise RuntimeError(f"{_WHO}: {name} must be on the boxes' device {b_t.device}, got {t.device}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{_WHO}: {name} must be contiguous (it is not copied silently)")
+    _ops.check_operands(_WHO, (("bboxes", b_t), ("transforms", transforms), ("centers", c_t), ("depths", d_t), ("categories", k_t),
+                               ("valid", v_t), ("sample_sizes", sizes), ("image_hw", hw_t)), b_t, "boxes'",
+                        required=("bboxes", "transforms", "sample_sizes"))
     dev = b_t.device
-    if dev.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: bboxes must be CUDA or CPU tensors, got {dev}")
+    _ops.check_backend(_WHO, "bboxes", dev)
     for name, t in (("bboxes", b_t), ("transforms", transforms), ("centers", c_t), ("depths", d_t)):
         if t is not None and t.is_floating_point() and t.dtype != torch.float32:
             raise TypeError(f"{_WHO}: {name} must be float32 (the definition is float32), got {t.dtype}")
-    if (b_t.dtype != torch.float32 or b_t.dim() != 3 or b_t.shape[2] != 4 or getattr(bboxes, "num_batch_dims", 1) != 1
-            or getattr(bboxes, "non_uniform_dim", 1) != 1):
-        raise RuntimeError(f"{_WHO}: bboxes must be float32 [F, G, 4] with one batch dimension and non_uniform_dim 1, "
-                           f"got {b_t.dtype} {tuple(b_t.shape)}")
-    F, G = int(b_t.shape[0]), int(b_t.shape[1])
+    F, G = _ops.check_bboxes(_WHO, bboxes, b_t, "[F, G, 4]")
     if transforms.dtype != torch.float32 or tuple(transforms.shape) != (F, 2, 3):
         raise RuntimeError(f"{_WHO}: transforms must be float32 [{F}, 2, 3], got {transforms.dtype} {tuple(transforms.shape)}")
     if c_t is not None and (c_t.dtype != torch.float32 or tuple(c_t.shape) != (F, G, 2)):
@@ -160,21 +142,11 @@ def camera_augment_boxes(bboxes, transforms: torch.Tensor, *, image_hw, centers=
         raise RuntimeError(f"{_WHO}: categories must be int32 or int64 [{F}, {G}], got {k_t.dtype} {tuple(k_t.shape)}")
     if v_t is not None and (v_t.dtype not in (torch.bool, torch.uint8) or tuple(v_t.shape) != (F, G)):
         raise RuntimeError(f"{_WHO}: valid must be bool or uint8 [{F}, {G}], got {v_t.dtype} {tuple(v_t.shape)}")
-    if sizes.dtype not in (torch.int32, torch.int64) or tuple(sizes.shape) != (F,):
-        raise RuntimeError(f"{_WHO}: sample_sizes must be int32 or int64 [{F}], got {sizes.dtype} {tuple(sizes.shape)}")
-    H = W = 0
-    if hw_t is not None:
-        if hw_t.dtype not in (torch.int32, torch.int64) or tuple(hw_t.shape) != (F, 2):
-            raise RuntimeError(f"{_WHO}: an image_hw tensor must be int32 or int64 [{F}, 2], got {hw_t.dtype} {tuple(hw_t.shape)}")
-    else:
-        if (not isinstance(image_hw, (list, tuple)) or len(image_hw) != 2
-                or any(isinstance(v, bool) or not isinstance(v, int) for v in image_hw)):
-            raise RuntimeError(f"{_WHO}: image_hw must be (H, W) Python ints or an integer tensor [F, 2], got {image_hw!r}")
-        H, W = (max(0, min(int(v), 1 << 24)) for v in image_hw)
-    if minimum_size is not None and (isinstance(minimum_size, bool) or not isinstance(minimum_size, (int, float))):
+    _ops.check_sample_sizes(_WHO, sizes, F)
+    H, W = _ops.image_hw_args(_WHO, image_hw, hw_t, F, "F")
+    if minimum_size is not None and not _ops.is_number(minimum_size):
         raise RuntimeError(f"{_WHO}: minimum_size must be a Python number or None, got {minimum_size!r}")
-    if G > MAX_BOXES:
-        raise RuntimeError(f"{_WHO}: {G} box slots per frame, at most MAX_BOXES = {MAX_BOXES} are supported")
+    _ops.check_box_count(_WHO, G, MAX_BOXES)
     m_in = _matrices(projection_matrices, F, dev)
 
     out_boxes = torch.empty_like(b_t)
@@ -190,7 +162,8 @@ def camera_augment_boxes(bboxes, transforms: torch.Tensor, *, image_hw, centers=
         prm = _nat.CameraBoxesParams()
         prm.minimum_size = float(minimum_size) if minimum_size is not None else 0.0
         prm.image_h, prm.image_w = H, W
-        prm.image_hw = hw_t.data_ptr() if hw_t is not None else None
+        ptr = _ops.ptr
+        prm.image_hw = ptr(hw_t)
         for i, (src, dst) in enumerate(zip(m_in, m_out)):
             prm.mat_in[i], prm.mat_out[i] = src.data_ptr(), dst.data_ptr()
             prm.mat_count[i] = src.shape[1] if src.dim() == 4 else 1
@@ -201,15 +174,10 @@ def camera_augment_boxes(bboxes, transforms: torch.Tensor, *, image_hw, centers=
         flags = ((_nat.CB_COUNTS_I64 if sizes.dtype == torch.int64 else 0)
                  | (_nat.CB_HW_I64 if hw_t is not None and hw_t.dtype == torch.int64 else 0)
                  | (_nat.CB_CATEGORIES_I64 if k_t is not None and k_t.dtype == torch.int64 else 0))
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         args = (b_t.data_ptr(), transforms.data_ptr(), ptr(c_t), ptr(d_t), ptr(k_t), ptr(v_t), sizes.data_ptr(), flags, F, G,
                 ctypes.addressof(prm), out_boxes.data_ptr(), ptr(out_centers), ptr(out_depths), ptr(out_cats), source.data_ptr(),
                 keep.data_ptr(), visible.data_ptr(), kept.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_camera_boxes(*args, _nat.stream_ptr(dev)), _WHO)
-        else:
-            _nat.check(_nat.lib().accv_camera_boxes_host(*args), _WHO)
+        _ops.run("accv_camera_boxes", args, dev, _WHO)
     rag = lambda t: RaggedBatch(t, sample_sizes=kept) if t is not None else None   # noqa: E731
     return CameraBoxes(rag(out_boxes), rag(out_centers), rag(out_depths), rag(out_cats), rag(source),
                        RaggedBatch(keep, sample_sizes=sizes), RaggedBatch(visible, sample_sizes=sizes), m_out)

@@ -17,6 +17,8 @@ from typing import List, NamedTuple, Sequence
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 MAX_TASKS = _nat.CD_MAX_TASKS
 MAX_MAPS = _nat.CD_MAX_MAPS
@@ -34,16 +36,10 @@ class CenterPointDetections(NamedTuple):
     source: object   # int32 [B, M], the peak rank k
 
 
-def _number(name, v, integer=False):
-    if isinstance(v, bool) or not isinstance(v, int if integer else (int, float)):
-        raise RuntimeError(f"{_WHO}: {name} must be a Python {'integer' if integer else 'number'}, got {v!r}")
-    return v
-
-
 def _numbers(name, v, n, exact=False):
     if not isinstance(v, (list, tuple)) or (len(v) != n if exact else len(v) < n):
         raise RuntimeError(f"{_WHO}: {name} must be a sequence of {'' if exact else 'at least '}{n} numbers, got {v!r}")
-    return [_number(f"{name}[{i}]", v[i]) for i in range(n)]
+    return [_ops.number(_WHO, f"{name}[{i}]", v[i]) for i in range(n)]
 
 
 def _class_lists(tasks):
@@ -78,8 +74,7 @@ def _check_peaks(t, p, ref):
         if not x.is_contiguous():
             raise RuntimeError(f"{_WHO}: peaks[{t}].{name} must be contiguous (it is not copied silently)")
     ref = s if ref is None else ref
-    if s.device.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: peaks must be CUDA or CPU tensors, got {s.device}")
+    _ops.check_backend(_WHO, "peaks", s.device)
     if s.dtype not in _DTYPES or s.dtype == torch.float64:
         raise RuntimeError(f"{_WHO}: peaks[{t}].scores must be float32, float16 or bfloat16, got {s.dtype}")
     if not 1 <= s.shape[1] <= MAX_K:
@@ -177,8 +172,6 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
     arithmetic.  The integer outputs and the exact channels of the two are equal; ``exp``, ``atan2`` and the sigmoid agree
     to a few ulp.  ``B == 0`` gives empty outputs without a launch.
     """
-    from ..batching_helpers import RaggedBatch
-
     T, first, ids = _class_lists(tasks)
     if hasattr(peaks, "scores"):
         peaks, feats = [peaks], [feats]
@@ -202,13 +195,13 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
     if H < 1 or W < 1 or H * W >= 2 ** 31:
         raise RuntimeError(f"{_WHO}: the maps must have H, W >= 1 and H * W < 2^31, got {H} x {W}")
     pc, vs = _numbers("pc_range", pc_range, 2), _numbers("voxel_size", voxel_size, 2)
-    factor = _number("out_size_factor", out_size_factor)
+    factor = _ops.number(_WHO, "out_size_factor", out_size_factor)
     if not (vs[0] > 0 and vs[1] > 0 and factor > 0 and all(math.isfinite(v) for v in (*vs, factor))):
         raise RuntimeError(f"{_WHO}: voxel_size and out_size_factor must be positive and finite, got {voxel_size!r}, "
                            f"{out_size_factor!r}")
     if not (math.isfinite(pc[0]) and math.isfinite(pc[1])):
         raise RuntimeError(f"{_WHO}: pc_range must be finite, got {pc_range!r}")
-    if score_threshold is not None and math.isnan(_number("score_threshold", score_threshold)):
+    if score_threshold is not None and math.isnan(_ops.number(_WHO, "score_threshold", score_threshold)):
         raise RuntimeError(f"{_WHO}: score_threshold must not be NaN")
     rng = None if post_center_range is None else _numbers("post_center_range", post_center_range, 6, exact=True)
     if rng is not None and any(math.isnan(v) for v in rng):
@@ -221,9 +214,9 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
         raise RuntimeError(f"{_WHO}: nms_threshold must be a number, a sequence of {T} numbers (one per task) or None, got "
                            f"{nms_threshold!r}")
     for t, v in enumerate(nms):
-        if v is not None and math.isnan(_number(f"nms_threshold[{t}]", v)):
+        if v is not None and math.isnan(_ops.number(_WHO, f"nms_threshold[{t}]", v)):
             raise RuntimeError(f"{_WHO}: nms_threshold[{t}] must not be NaN")
-    if post_max_size is not None and _number("post_max_size", post_max_size, integer=True) < 1:
+    if post_max_size is not None and _ops.number(_WHO, "post_max_size", post_max_size, integer=True) < 1:
         raise RuntimeError(f"{_WHO}: post_max_size must be at least 1, got {post_max_size}")
 
     dev = scores0.device
@@ -258,11 +251,7 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
             p.class_ids[n] = v
         args = (ctypes.addressof(p), B, K, H, W, M, boxes.data_ptr(), out_scores.data_ptr(), labels.data_ptr(),
                 source.data_ptr(), kept.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_center_point_decode(*args, _nat.stream_ptr(dev)), _WHO)
-        else:
-            _nat.check(_nat.lib().accv_center_point_decode_host(*args), _WHO)
+        _ops.run("accv_center_point_decode", args, dev, _WHO)
     out = []
     for t, sizes_t in enumerate(kept.unbind(0)):     # one sample_sizes tensor per task, shared by its four outputs
         out.append(CenterPointDetections(*(RaggedBatch(x[t], sample_sizes=sizes_t) for x in (boxes, out_scores, labels, source))))

@@ -25,15 +25,13 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 _DTYPES = _nat.FLOAT_DTYPE_CODES
 _KINDS = {"l1": _nat.CR_L1, "smooth_l1": _nat.CR_SMOOTH_L1}
 MAX_MAPS = _nat.CR_MAX_MAPS
 MAX_CHANNELS = _nat.CR_MAX_CHANNELS
-
-
-def _is_ragged(x) -> bool:
-    return hasattr(x, "tensor") and hasattr(x, "sample_sizes")
 
 
 def _check_feats(who, feats):
@@ -72,7 +70,7 @@ def _check_feats(who, feats):
 
 
 def _check_ragged_centers(who, centers, first):
-    if not _is_ragged(centers):
+    if not _ops.is_ragged(centers):
         raise RuntimeError(f"{who}: centers must be a RaggedBatch of int32 [B, Nmax, 2] (x, y)")
     c_t, sizes = centers.tensor, centers.sample_sizes
     for name, t in (("centers", c_t), ("sample_sizes", sizes)):
@@ -111,7 +109,7 @@ class _Call:
 
     def geometry(self, where, sizes):
         return (ctypes.addressof(self.channels), self.n, self.dtype, self.B, self.H, self.W, where.data_ptr(),
-                None if sizes is None else sizes.data_ptr(), self.N)
+                _ops.ptr(sizes), self.N)
 
     def empty_maps(self, needed):
         """uninitialised gradient maps (contiguous, as the maps are) where `needed`, None elsewhere"""
@@ -167,7 +165,7 @@ class _CenterRegressionLoss(torch.autograd.Function):
             with _nat.device_guard(dev):
                 _nat.check(lib.accv_center_regression_loss(
                     ctypes.addressof(ptrs), *call.geometry(where, sizes), flags, targets.data_ptr(),
-                    None if weights is None else weights.data_ptr(), ctypes.addressof(params),
+                    _ops.ptr(weights), ctypes.addressof(params),
                     avg_factor.data_ptr() if isinstance(avg_factor, torch.Tensor) else None, loss.data_ptr(),
                     denom.data_ptr(), ws.data_ptr(), ws.numel(), _nat.stream_ptr(dev)), "center_regression_loss")
         ctx.call, ctx.flags, ctx.params = call, flags, params
@@ -190,7 +188,7 @@ class _CenterRegressionLoss(torch.autograd.Function):
             with _nat.device_guard(call.dev):
                 _nat.check(_nat.lib().accv_center_regression_loss_bwd(
                     ctypes.addressof(feat_ptrs), ctypes.addressof(grad_ptrs), *call.geometry(where, sizes), ctx.flags,
-                    targets.data_ptr(), None if weights is None else weights.data_ptr(), ctypes.addressof(ctx.params),
+                    targets.data_ptr(), _ops.ptr(weights), ctypes.addressof(ctx.params),
                     grad.data_ptr(), denom.data_ptr(), _nat.stream_ptr(call.dev)), "center_regression_loss backward")
         return (None, None, None, None, None, None, None, *grads)
 
@@ -231,7 +229,7 @@ def gather_at_centers(feats: Union[torch.Tensor, Sequence[torch.Tensor]], where)
     who = "gather_at_centers"
     maps = _check_feats(who, feats)
     first = maps[0]
-    if _is_ragged(where):
+    if _ops.is_ragged(where):
         call_where, call_sizes = _check_ragged_centers(who, where, first)
         call = _Call(maps, call_where, call_sizes, False)
     else:
@@ -247,9 +245,7 @@ def gather_at_centers(feats: Union[torch.Tensor, Sequence[torch.Tensor]], where)
         call_where, call_sizes = where, None
         call = _Call(maps, where, None, True)
     out = _GatherAtCenters.apply(call, call_where, call_sizes, *maps)
-    from ..batching_helpers import RaggedBatch
-
-    return RaggedBatch(out, sample_sizes=where.sample_sizes) if _is_ragged(where) else out
+    return RaggedBatch(out, sample_sizes=where.sample_sizes) if _ops.is_ragged(where) else out
 
 
 def center_regression_loss(feats: Union[torch.Tensor, Sequence[torch.Tensor]], centers, targets, weights=None, *,
@@ -290,8 +286,7 @@ def center_regression_loss(feats: Union[torch.Tensor, Sequence[torch.Tensor]], c
     if kind == "smooth_l1" and not (float(beta) > 0.0):
         raise RuntimeError(f"{who}: smooth_l1 needs beta > 0, got {beta}")
     B, N, C = first.shape[0], c_t.shape[1], sum(m.shape[1] for m in maps)
-    targets = targets.tensor if _is_ragged(targets) else targets
-    weights = weights.tensor if _is_ragged(weights) else weights
+    targets, weights = _ops.tensor_of(targets), _ops.tensor_of(weights)
     for name, t, shapes in (("targets", targets, ((B, N, C),)), ("weights", weights, ((B, N), (B, N, C)))):
         if t is None and name == "weights":
             continue

@@ -15,6 +15,8 @@ from typing import List, NamedTuple, Sequence
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 MAX_TASKS = _nat.CT_MAX_TASKS
 MAX_CLASSES = _nat.CT_MAX_CLASSES
@@ -31,20 +33,10 @@ class CenterPointTargets(NamedTuple):
     source: object    # int32 [B, M], the input slot
 
 
-def _is_ragged(x) -> bool:
-    return hasattr(x, "tensor") and hasattr(x, "sample_sizes")
-
-
-def _number(name, v, integer=False):
-    if isinstance(v, bool) or not isinstance(v, int if integer else (int, float)):
-        raise RuntimeError(f"{_WHO}: {name} must be a Python {'integer' if integer else 'number'}, got {v!r}")
-    return v
-
-
 def _pair(name, v, integer=False):
     if not isinstance(v, (list, tuple)) or len(v) < 2:
         raise RuntimeError(f"{_WHO}: {name} must be a sequence of at least two numbers, got {v!r}")
-    return _number(f"{name}[0]", v[0], integer), _number(f"{name}[1]", v[1], integer)
+    return _ops.number(_WHO, f"{name}[0]", v[0], integer), _ops.number(_WHO, f"{name}[1]", v[1], integer)
 
 
 def _class_table(tasks):
@@ -111,33 +103,25 @@ def center_point_targets(boxes, labels, tasks: Sequence[Sequence[int]], *, pc_ra
     integer outputs of the two are equal; the ``log`` / ``sin`` / ``cos`` channels agree to a few ulp.  Nothing takes a
     gradient.  ``B == 0`` or ``M == 0`` gives empty outputs without a launch.
     """
-    from ..batching_helpers import RaggedBatch
-
-    if not _is_ragged(boxes):
+    if not _ops.is_ragged(boxes):
         raise RuntimeError(f"{_WHO}: boxes must be a RaggedBatch of float32 [B, Nmax, D]")
     b_t, sizes = boxes.tensor, boxes.sample_sizes
-    l_t = labels.tensor if _is_ragged(labels) else labels
-    for name, t in (("boxes", b_t), ("labels", l_t), ("sample_sizes", sizes)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: {name} must be a tensor")
-        if t.device != b_t.device:
-            raise RuntimeError(f"{_WHO}: {name} must be on the boxes' device {b_t.device}, got {t.device}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{_WHO}: {name} must be contiguous (it is not copied silently)")
-    if b_t.device.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: boxes must be CUDA or CPU tensors, got {b_t.device}")
+    l_t = _ops.tensor_of(labels)
+    _ops.check_operands(_WHO, (("boxes", b_t), ("labels", l_t), ("sample_sizes", sizes)), b_t, "boxes'",
+                        required=("boxes", "labels", "sample_sizes"))
+    _ops.check_backend(_WHO, "boxes", b_t.device)
     if b_t.dtype != torch.float32 or b_t.dim() != 3 or b_t.shape[2] not in (7, 9):
         raise RuntimeError(f"{_WHO}: boxes must be float32 [B, Nmax, 7 or 9], got {b_t.dtype} {tuple(b_t.shape)}")
     B, N, D = b_t.shape
     if l_t.dtype not in (torch.int32, torch.int64) or tuple(l_t.shape) != (B, N):
         raise RuntimeError(f"{_WHO}: labels must be int32 or int64 [{B}, {N}], got {l_t.dtype} {tuple(l_t.shape)}")
-    if sizes.dtype not in (torch.int32, torch.int64) or tuple(sizes.shape) != (B,):
-        raise RuntimeError(f"{_WHO}: sample_sizes must be int32 or int64 [{B}], got {sizes.dtype} {tuple(sizes.shape)}")
+    _ops.check_sample_sizes(_WHO, sizes, B)
     T, task_of, pos_of = _class_table(tasks)
     pc, vs = _pair("pc_range", pc_range), _pair("voxel_size", voxel_size)
     W, H = _pair("grid_size", grid_size, integer=True)
-    factor, overlap = _number("out_size_factor", out_size_factor), _number("gaussian_overlap", gaussian_overlap)
-    min_radius, max_objs = _number("min_radius", min_radius, True), _number("max_objs", max_objs, True)
+    factor = _ops.number(_WHO, "out_size_factor", out_size_factor)
+    overlap = _ops.number(_WHO, "gaussian_overlap", gaussian_overlap)
+    min_radius, max_objs = _ops.number(_WHO, "min_radius", min_radius, True), _ops.number(_WHO, "max_objs", max_objs, True)
     if not (vs[0] > 0 and vs[1] > 0 and factor > 0 and math.isfinite(vs[0]) and math.isfinite(vs[1]) and math.isfinite(factor)):
         raise RuntimeError(f"{_WHO}: voxel_size and out_size_factor must be positive and finite, got {voxel_size!r}, "
                            f"{out_size_factor!r}")
@@ -168,11 +152,7 @@ def center_point_targets(boxes, labels, tasks: Sequence[Sequence[int]], *, pc_ra
         args = (b_t.data_ptr(), l_t.data_ptr(), sizes.data_ptr(), flags, B, N, D, W, H, M, ctypes.addressof(params),
                 centers.data_ptr(), radii.data_ptr(), out_labels.data_ptr(), targets.data_ptr(), indices.data_ptr(),
                 source.data_ptr(), kept.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_center_point_targets(*args, _nat.stream_ptr(dev)), _WHO)
-        else:
-            _nat.check(_nat.lib().accv_center_point_targets_host(*args), _WHO)
+        _ops.run("accv_center_point_targets", args, dev, _WHO)
     out = []
     for t, sizes_t in enumerate(kept.unbind(0)):     # one sample_sizes tensor per task, shared by its six outputs
         out.append(CenterPointTargets(*(RaggedBatch(x[t], sample_sizes=sizes_t)

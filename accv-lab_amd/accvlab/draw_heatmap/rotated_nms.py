@@ -13,6 +13,8 @@ from typing import List
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 from .center_decode import CenterPointDetections
 
 MAX_TASKS = _nat.RN_MAX_TASKS
@@ -75,8 +77,6 @@ def rotated_iou_bev(boxes_a, boxes_b):
     metres apart along their length.  Nothing takes a gradient.  GPU tensors run one HIP kernel on
     torch's current stream, CPU tensors the library's serial host entry over the same arithmetic.
     """
-    from ..batching_helpers import RaggedBatch
-
     ta, tb = [_check_tensor(_IOU, name, getattr(x, "tensor", None), torch.float32, 3, "[B, N, 5]")
               for name, x in (("boxes_a", boxes_a), ("boxes_b", boxes_b))]
     if ta.shape[2] != 5 or tb.shape[2] != 5:
@@ -91,11 +91,7 @@ def rotated_iou_bev(boxes_a, boxes_b):
     out = torch.empty((B, Na, Nb), dtype=torch.float32, device=dev)
     if out.numel():
         args = (ta.data_ptr(), sa.data_ptr(), tb.data_ptr(), sb.data_ptr(), B, Na, Nb, out.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_rotated_iou_bev(*args, _nat.stream_ptr(dev)), _IOU)
-        else:
-            _nat.check(_nat.lib().accv_rotated_iou_bev_host(*args), _IOU)
+        _ops.run("accv_rotated_iou_bev", args, dev, _IOU)
     return RaggedBatch(out, sample_sizes=sa)
 
 
@@ -117,7 +113,7 @@ def _check_task(t, det, ref):
     dtypes = (torch.float32, torch.float32, torch.int64, torch.int32)
     tensors = []
     for name, x, dtype in zip(names, det, dtypes):
-        if not hasattr(x, "tensor") or not hasattr(x, "sample_sizes"):
+        if not _ops.is_ragged(x):
             raise RuntimeError(f"{_NMS}: detections[{t}].{name} must be a RaggedBatch")
         rank = 3 if name == "boxes" else 2
         tensors.append(_check_tensor(_NMS, f"detections[{t}].{name}", x.tensor, dtype, rank, "[B, N, D]" if rank == 3 else "[B, N]"))
@@ -185,8 +181,6 @@ def rotated_nms_bev(detections, iou_threshold, *, pre_max_size=None, post_max_si
     no atomics, no workspace, no host synchronisation, bitwise reproducible); CPU tensors run the library's serial host
     entry over the same arithmetic.  ``B == 0`` gives empty outputs without a launch.
     """
-    from ..batching_helpers import RaggedBatch
-
     if hasattr(detections, "boxes") or (isinstance(detections, (list, tuple)) and len(detections) == 4
                                         and all(hasattr(x, "sample_sizes") for x in detections)):
         detections = [detections]
@@ -232,11 +226,7 @@ def rotated_nms_bev(detections, iou_threshold, *, pre_max_size=None, post_max_si
         p.num_tasks = T
         args = (ctypes.addressof(p), B, N, D, N if pre is None else pre, M, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
                 source.data_ptr(), kept.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_rotated_nms_bev(*args, _nat.stream_ptr(dev)), _NMS)
-        else:
-            _nat.check(_nat.lib().accv_rotated_nms_bev_host(*args), _NMS)
+        _ops.run("accv_rotated_nms_bev", args, dev, _NMS)
     out = []
     for t, sizes_t in enumerate(kept.unbind(0)):     # one sample_sizes tensor per task, shared by its four outputs
         out.append(CenterPointDetections(*(RaggedBatch(x[t], sample_sizes=sizes_t) for x in (boxes, scores, labels, source))))

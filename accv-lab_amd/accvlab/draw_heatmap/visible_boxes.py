@@ -15,13 +15,11 @@ import ctypes
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from ..batching_helpers import RaggedBatch
 
 MAX_BOXES = _nat.VB_MAX_BOXES
 _WHO = "visible_bbox_mask"
-
-
-def _is_ragged(x) -> bool:
-    return hasattr(x, "tensor") and hasattr(x, "sample_sizes")
 
 
 def visible_bbox_mask(bboxes, depths=None, *, image_hw, check_occlusion: bool = True, minimum_size=None,
@@ -60,57 +58,28 @@ def visible_bbox_mask(bboxes, depths=None, *, image_hw, check_occlusion: bool = 
     bitwise reproducible); CPU tensors run the library's host entry over the same integer algorithm, with equal results.
     Nothing takes a gradient.
     """
-    from ..batching_helpers import RaggedBatch
-
-    if not _is_ragged(bboxes):
+    if not _ops.is_ragged(bboxes):
         raise RuntimeError(f"{_WHO}: bboxes must be a RaggedBatch of float32 [B, G_max, 4]")
     b_t, sizes = bboxes.tensor, bboxes.sample_sizes
     if not check_occlusion and minimum_size is None:
         raise RuntimeError(f"{_WHO}: at least one of check_occlusion and minimum_size must be requested")
     if check_occlusion and depths is None:
         raise RuntimeError(f"{_WHO}: check_occlusion needs depths")
-    d_t = None
-    if check_occlusion:
-        d_t = depths.tensor if _is_ragged(depths) else depths
+    d_t = _ops.tensor_of(depths) if check_occlusion else None
     hw_t = image_hw if isinstance(image_hw, torch.Tensor) else None
-    for name, t in (("bboxes", b_t), ("depths", d_t), ("sample_sizes", sizes), ("image_hw", hw_t)):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: {name} must be a tensor")
-        if t.device != b_t.device:
-            raise RuntimeError(f"{_WHO}: {name} must be on the boxes' device {b_t.device}, got {t.device}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{_WHO}: {name} must be contiguous (it is not copied silently)")
-    if b_t.device.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{_WHO}: bboxes must be CUDA or CPU tensors, got {b_t.device}")
-    if b_t.is_floating_point() and b_t.dtype != torch.float32:
-        raise TypeError(f"{_WHO}: bboxes must be float32 (the definition is float32), got {b_t.dtype}")
-    if (b_t.dtype != torch.float32 or b_t.dim() != 3 or b_t.shape[2] != 4 or getattr(bboxes, "num_batch_dims", 1) != 1
-            or getattr(bboxes, "non_uniform_dim", 1) != 1):
-        raise RuntimeError(f"{_WHO}: bboxes must be float32 [B, G_max, 4] with one batch dimension and non_uniform_dim 1, "
-                           f"got {b_t.dtype} {tuple(b_t.shape)}")
-    B, G = int(b_t.shape[0]), int(b_t.shape[1])
+    _ops.check_operands(_WHO, (("bboxes", b_t), ("depths", d_t), ("sample_sizes", sizes), ("image_hw", hw_t)), b_t, "boxes'")
+    _ops.check_backend(_WHO, "bboxes", b_t.device)
+    _ops.check_float32(_WHO, "bboxes", b_t)
+    B, G = _ops.check_bboxes(_WHO, bboxes, b_t, "[B, G_max, 4]")
     if d_t is not None:
-        if d_t.is_floating_point() and d_t.dtype != torch.float32:
-            raise TypeError(f"{_WHO}: depths must be float32 (the definition is float32), got {d_t.dtype}")
+        _ops.check_float32(_WHO, "depths", d_t)
         if d_t.dtype != torch.float32 or tuple(d_t.shape) != (B, G):
             raise RuntimeError(f"{_WHO}: depths must be float32 [{B}, {G}], got {d_t.dtype} {tuple(d_t.shape)}")
-    if sizes.dtype not in (torch.int32, torch.int64) or tuple(sizes.shape) != (B,):
-        raise RuntimeError(f"{_WHO}: sample_sizes must be int32 or int64 [{B}], got {sizes.dtype} {tuple(sizes.shape)}")
-    H = W = 0
-    if hw_t is not None:
-        if hw_t.dtype not in (torch.int32, torch.int64) or tuple(hw_t.shape) != (B, 2):
-            raise RuntimeError(f"{_WHO}: an image_hw tensor must be int32 or int64 [{B}, 2], got {hw_t.dtype} {tuple(hw_t.shape)}")
-    else:
-        if (not isinstance(image_hw, (list, tuple)) or len(image_hw) != 2
-                or any(isinstance(v, bool) or not isinstance(v, int) for v in image_hw)):
-            raise RuntimeError(f"{_WHO}: image_hw must be (H, W) Python ints or an integer tensor [B, 2], got {image_hw!r}")
-        H, W = (max(0, min(int(v), 1 << 24)) for v in image_hw)
-    if minimum_size is not None and (isinstance(minimum_size, bool) or not isinstance(minimum_size, (int, float))):
+    _ops.check_sample_sizes(_WHO, sizes, B)
+    H, W = _ops.image_hw_args(_WHO, image_hw, hw_t, B, "B")
+    if minimum_size is not None and not _ops.is_number(minimum_size):
         raise RuntimeError(f"{_WHO}: minimum_size must be a Python number or None, got {minimum_size!r}")
-    if G > MAX_BOXES:
-        raise RuntimeError(f"{_WHO}: {G} box slots per frame, at most MAX_BOXES = {MAX_BOXES} are supported")
+    _ops.check_box_count(_WHO, G, MAX_BOXES)
 
     dev = b_t.device
     out = torch.empty((B, G), dtype=torch.bool, device=dev)
@@ -119,13 +88,9 @@ def visible_bbox_mask(bboxes, depths=None, *, image_hw, check_occlusion: bool = 
                                          1 if check_occlusion else 0, 0 if minimum_size is None else 1, 1 if shrink_to_int else 0)
         flags = ((_nat.VB_COUNTS_I64 if sizes.dtype == torch.int64 else 0)
                  | (_nat.VB_HW_I64 if hw_t is not None and hw_t.dtype == torch.int64 else 0))
-        args = (b_t.data_ptr(), d_t.data_ptr() if d_t is not None else None, sizes.data_ptr(),
-                hw_t.data_ptr() if hw_t is not None else None, flags, B, G, ctypes.addressof(params), out.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_visible_boxes(*args, _nat.stream_ptr(dev)), _WHO)
-        else:
-            _nat.check(_nat.lib().accv_visible_boxes_host(*args), _WHO)
+        args = (b_t.data_ptr(), _ops.ptr(d_t), sizes.data_ptr(), _ops.ptr(hw_t), flags, B, G, ctypes.addressof(params),
+                out.data_ptr())
+        _ops.run("accv_visible_boxes", args, dev, _WHO)
     return RaggedBatch(out, sample_sizes=sizes)
 
 

@@ -14,6 +14,7 @@ import ctypes
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
 from . import prepare as _prep
 
 MAX_EXTENT = _nat.IP_MAX_EXTENT
@@ -43,7 +44,7 @@ def nv12_planes(surfaces, hw, *, uv_row=None):
     B, rows, pitch = (int(v) for v in surfaces.shape)
     Hc, Wc = (H + 1) // 2, (W + 1) // 2
     first = H if uv_row is None else uv_row
-    if not _prep._is_int(first) or first < H:
+    if not _ops.is_int(first) or first < H:
         raise RuntimeError(f"{who}: uv_row must be a Python int of at least H = {H}, got {uv_row!r}")
     if pitch < 2 * Wc:
         raise RuntimeError(f"{who}: a pitch of {pitch} bytes is too small for {Wc} chroma pairs ({2 * Wc} bytes) of width {W}")
@@ -149,11 +150,7 @@ def nv12_to_rgb(y, uv, *, full_range=False, as_bgr=False, chroma_order="uv", out
         p = _nat.Nv12Params()
         planes.fill(p)
         args = (y.data_ptr(), uv.data_ptr(), ctypes.addressof(p), result.data_ptr())
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_nv12_to_rgb(*args, _nat.stream_ptr(dev)), who)
-        else:
-            _nat.check(_nat.lib().accv_nv12_to_rgb_host(*args), who)
+        _ops.run("accv_nv12_to_rgb", args, dev, who)
     return result
 
 

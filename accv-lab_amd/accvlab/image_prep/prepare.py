@@ -15,6 +15,8 @@ import math
 import torch
 
 from .. import _amd_native as _nat
+from .._amd_native import operands as _ops
+from .._amd_native.operands import is_int, is_number
 
 MAX_EXTENT = _nat.IP_MAX_EXTENT
 TILE_W = _nat.IP_TILE_W
@@ -28,22 +30,14 @@ CHANNEL_PERMUTATIONS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (2, 1, 0), (2, 0, 1), (
 IDENTITY_PHOTOMETRIC = (0.0, 1.0, 1.0, 0.0, 1.0, 0.0)
 
 
-def _is_int(v) -> bool:
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
-def _is_number(v) -> bool:
-    return isinstance(v, (int, float)) and not isinstance(v, bool)
-
-
 def _hw(name, v, who=_WHO):
-    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_is_int(x) for x in v):
+    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(is_int(x) for x in v):
         raise RuntimeError(f"{who}: {name} must be (height, width) Python ints, got {v!r}")
     return int(v[0]), int(v[1])
 
 
 def _tile(tile_hw, who=_WHO):
-    t = (tile_hw, tile_hw) if _is_int(tile_hw) else _hw("tile_hw", tile_hw, who)
+    t = (tile_hw, tile_hw) if is_int(tile_hw) else _hw("tile_hw", tile_hw, who)
     if not all(1 <= x <= MAX_EXTENT for x in t):
         raise RuntimeError(f"{who}: tile_hw must be at least 1 and at most {MAX_EXTENT}, got {tile_hw!r}")
     return t
@@ -104,12 +98,12 @@ def sample_photometric_params(num_groups, views_per_group, *, min_max_brightness
     are, so the stream of a seeded generator does not depend on them.
     """
     who = "sample_photometric_params"
-    if not _is_int(num_groups) or not _is_int(views_per_group) or num_groups < 0 or views_per_group < 1:
+    if not is_int(num_groups) or not is_int(views_per_group) or num_groups < 0 or views_per_group < 1:
         raise RuntimeError(f"{who}: num_groups >= 0 and views_per_group >= 1 Python ints, got {num_groups!r}, {views_per_group!r}")
     ranges = {}
     for name, v in (("min_max_brightness", min_max_brightness), ("min_max_hue", min_max_hue),
                     ("min_max_contrast", min_max_contrast), ("min_max_saturation", min_max_saturation)):
-        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_is_number(x) and math.isfinite(x) for x in v) or v[0] > v[1]:
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(is_number(x) and math.isfinite(x) for x in v) or v[0] > v[1]:
             raise RuntimeError(f"{who}: {name} must be (min, max) finite Python numbers with min <= max, got {v!r}")
         ranges[name] = (float(v[0]), float(v[1]))
     r = torch.rand((num_groups, 11), generator=generator, dtype=torch.float64)
@@ -139,9 +133,9 @@ def sample_photometric_params(num_groups, views_per_group, *, min_max_brightness
 
 
 def _three(name, v, who=_WHO):
-    if _is_number(v):
+    if is_number(v):
         v = (v, v, v)
-    if not isinstance(v, (list, tuple)) or len(v) != 3 or not all(_is_number(x) and math.isfinite(x) for x in v):
+    if not isinstance(v, (list, tuple)) or len(v) != 3 or not all(is_number(x) and math.isfinite(x) for x in v):
         raise RuntimeError(f"{who}: {name} must be a finite Python number or three of them, got {v!r}")
     return tuple(float(x) for x in v)
 
@@ -221,19 +215,9 @@ def _prepare(images, output_hw, transforms, source_hw, photometric, is_bgr, mean
     rest = (ptr(source_hw), ptr(transforms), ptr(photometric), ctypes.addressof(full), ptr(result))
     if B > 0 and planes is not None:
         planes.fill(full.planes)
-        args = (ptr(planes.y), ptr(planes.uv), *rest)
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_prepare_images_nv12(*args, _nat.stream_ptr(dev)), who)
-        else:
-            _nat.check(_nat.lib().accv_prepare_images_nv12_host(*args), who)
+        _ops.run("accv_prepare_images_nv12", (ptr(planes.y), ptr(planes.uv), *rest), dev, who)
     elif B > 0:
-        args = (ptr(images), *rest)
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(_nat.lib().accv_prepare_images(*args, _nat.stream_ptr(dev)), who)
-        else:
-            _nat.check(_nat.lib().accv_prepare_images_host(*args, ptr(coords)), who)
+        _ops.run("accv_prepare_images", (ptr(images), *rest), dev, who, (ptr(coords),))   # coords: the host entry only
     return result
 
 

@@ -33,24 +33,25 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .prepare import _hw, _is_int, _is_number, output_size_transform
+from .._amd_native.operands import is_int, is_number
+from .prepare import _hw, output_size_transform
 
 _BORDERS = ("top", "left", "bottom", "right")
 
 
 def _prob(who, p):
-    if not _is_number(p) or not 0.0 <= p <= 1.0:
+    if not is_number(p) or not 0.0 <= p <= 1.0:
         raise RuntimeError(f"{who}: prob must be a number in [0, 1], got {p!r}")
 
 
 def _pair(who, name, v):
-    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_is_number(x) and math.isfinite(x) for x in v):
+    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(is_number(x) and math.isfinite(x) for x in v):
         raise RuntimeError(f"{who}: {name} must be two finite numbers (x, y), got {v!r}")
     return float(v[0]), float(v[1])
 
 
 def _scalar_range(who, lo, hi):
-    if not _is_number(lo) or not math.isfinite(lo) or (hi is not None and (not _is_number(hi) or not math.isfinite(hi) or hi < lo)):
+    if not is_number(lo) or not math.isfinite(lo) or (hi is not None and (not is_number(hi) or not math.isfinite(hi) or hi < lo)):
         raise RuntimeError(f"{who}: min must be a finite number and max, if given, a finite number not below it, got {lo!r}, {hi!r}")
 
 
@@ -226,7 +227,7 @@ class Selection:
         if (not isinstance(self.option_probs, (list, tuple)) or not isinstance(self.options, (list, tuple))
                 or len(self.option_probs) != len(self.options) or not self.options):
             raise RuntimeError("Selection: option_probs and options must be sequences of one non-zero length")
-        if not all(_is_number(p) and p >= 0 for p in self.option_probs) or abs(sum(self.option_probs) - 1.0) > 1e-6:
+        if not all(is_number(p) and p >= 0 for p in self.option_probs) or abs(sum(self.option_probs) - 1.0) > 1e-6:
             raise RuntimeError(f"Selection: option_probs must be non-negative and sum to 1, got {self.option_probs!r}")
         for o in self.sequences:
             for s in o:
@@ -296,7 +297,7 @@ def sample_image_transforms(num_groups, views_per_group, steps, *, source_hw, ou
     ``Rotation`` or a ``Shearing``.
     """
     who = "sample_image_transforms"
-    if not _is_int(num_groups) or not _is_int(views_per_group) or num_groups < 0 or views_per_group < 1:
+    if not is_int(num_groups) or not is_int(views_per_group) or num_groups < 0 or views_per_group < 1:
         raise RuntimeError(f"{who}: num_groups >= 0 and views_per_group >= 1 Python ints, got {num_groups!r}, {views_per_group!r}")
     if not isinstance(steps, (list, tuple)) or not all(hasattr(s, "prob") and hasattr(s, "draws") for s in steps):
         raise RuntimeError(f"{who}: steps must be a sequence of step descriptors")

@@ -16,6 +16,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ... import _amd_native as _nat
+from ..._amd_native import operands as _ops
 
 try:  # C++ fast path of the fixed-size CUDA calls (built by `make -C accv-lab_amd/csrc_host`); the code below is complete without it
     from . import _lane_host as _lh
@@ -186,18 +187,18 @@ def _backward(points, distances, p_sizes, d_sizes, relative, grad_out, grad_leng
     grad_out = grad_out.contiguous().to(points.dtype) if grad_out is not None else None
     grad_lengths = grad_lengths.contiguous().to(points.dtype) if grad_lengths is not None else None
     p_sizes, d_sizes, c64 = _count_args(p_sizes, d_sizes)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    ptr = _ops.ptr
     code = _DTYPE_CODE[points.dtype]
     args = (ptr(points), ptr(distances), ptr(p_sizes), ptr(d_sizes), ptr(grad_out), ptr(grad_lengths), ptr(grad_p),
             ptr(grad_d), b, pmax, qmax, dims, code, c64, int(bool(relative)))
-    lib = _nat.lib()
-    if points.is_cuda:
-        with _nat.device_guard(points.device):
-            wb = _grad_workspace_bytes(b, pmax, qmax, dims, code)
-            ws = torch.empty(wb, dtype=torch.uint8, device=points.device) if wb else None
-            _nat.check(lib.accv_polyline_grad(*args, ptr(ws), wb, _nat.stream_ptr(points.device)), "polyline backward")
+    who = "polyline backward"
+    if points.is_cuda:   # the device entry takes a workspace, the host entry a thread count (0: its default)
+        wb = _grad_workspace_bytes(b, pmax, qmax, dims, code)
+        ws = torch.empty(wb, dtype=torch.uint8, device=points.device) if wb else None
+        args += (ptr(ws), wb)
     else:
-        _nat.check(lib.accv_polyline_grad_host(*args, 0), "polyline backward (host)")
+        who += " (host)"
+    _ops.run("accv_polyline_grad", args, points.device, who, host_extra=(0,))
     return grad_p, grad_d
 
 

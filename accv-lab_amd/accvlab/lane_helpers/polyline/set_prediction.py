@@ -27,6 +27,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ... import _amd_native as _nat
+from ..._amd_native import operands as _ops
 from ...batching_helpers import _matched_pairs as _mp
 from ...batching_helpers.assignment import batched_linear_sum_assignment
 from ...batching_helpers.ragged import RaggedBatch
@@ -149,7 +150,7 @@ def batched_polyline_matching_cost(pred_lines: Optional[torch.Tensor], gt_lines:
         p.class_weight, p.pts_weight, p.filler = class_weight, pts_weight, float(filler)
         p.focal_alpha, p.focal_gamma, p.focal_eps = float(focal_alpha), float(focal_gamma), float(focal_eps)
         p.pred_stride_b, p.pred_stride_q, p.class_kind = sb, sq, _KINDS[class_cost]
-        p.gt_closed = None if closed is None else closed.data_ptr()
+        p.gt_closed = _ops.ptr(closed)
         flags = ((_nat.PM_REVERSIBLE if reversible else 0) | closed_flag
                  | (_nat.PM_LABELS_I64 if labels is not None and labels.dtype == torch.int64 else 0))
         args = (pred_lines.data_ptr() if gt is not None else 0, gt.data_ptr() if gt is not None else 0,
@@ -157,12 +158,7 @@ def batched_polyline_matching_cost(pred_lines: Optional[torch.Tensor], gt_lines:
                 counts.data_ptr(), _DTYPES[dtype], flags, B, Q, G, P, D, int(scores.shape[2]) if scores is not None else 0,
                 scores.stride(0) if scores is not None else 0, scores.stride(1) if scores is not None else 0,
                 ctypes.addressof(p), out.data_ptr())
-        lib = _nat.lib()
-        if dev.type == "cuda":
-            with _nat.device_guard(dev):
-                _nat.check(lib.accv_polyline_matching_cost(*args, _nat.stream_ptr(dev)), who)
-        else:
-            _nat.check(lib.accv_polyline_matching_cost_host(*args), who)
+        _ops.run("accv_polyline_matching_cost", args, dev, who)
     return sizes_rb.create_with_sample_sizes_like_self(out, non_uniform_dim=2)
 
 

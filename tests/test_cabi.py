@@ -42,6 +42,50 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(nat.SIGNATURES), declared ^ set(nat.SIGNATURES)
 
 
+def test_blocking_entries_are_the_host_entries_and_the_two_copier_waits():
+    """_BLOCKING is computed from SIGNATURES; this is the set that was written out by hand before"""
+    from accvlab import _amd_native as nat
+
+    assert nat._BLOCKING == {
+        "accv_mtc_async_wait", "accv_mtc_stage_h2d", "accv_mtc_pack_host", "accv_polyline_sample_host",
+        "accv_polyline_grad_host", "accv_linear_assignment_host", "accv_matching_cost_host",
+        "accv_matched_focal_loss_host", "accv_matched_focal_loss_bwd_host", "accv_matched_box_loss_host",
+        "accv_matched_box_loss_bwd_host", "accv_polyline_matching_cost_host", "accv_matched_polyline_loss_host",
+        "accv_matched_polyline_loss_bwd_host", "accv_center_point_targets_host", "accv_bev_augment_host",
+        "accv_center_point_decode_host", "accv_rotated_iou_bev_host", "accv_rotated_nms_bev_host",
+        "accv_visible_boxes_host", "accv_box_heatmap_host", "accv_camera_boxes_host", "accv_prepare_images_host",
+        "accv_nv12_to_rgb_host", "accv_prepare_images_nv12_host"}
+
+
+def test_device_twin_of_a_host_entry_takes_the_same_arguments_and_a_stream():
+    """What operands.run() rests on: accv_X takes the arguments of accv_X_host and then the stream.  The exceptions are
+    named: accv_prepare_images_host has its coords output where the stream is; a device entry with a workspace takes
+    (pointer, bytes) in front of the stream, and its caller appends them; the two polyline host entries end in a thread
+    count, which their callers pass as host_extra."""
+    from accvlab import _amd_native as nat
+
+    vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    workspace = {"accv_linear_assignment", "accv_matched_focal_loss", "accv_matched_box_loss", "accv_matched_polyline_loss"}
+    threads = {"accv_polyline_sample", "accv_polyline_grad"}
+    twins = 0
+    for host, (res, host_args) in nat.SIGNATURES.items():
+        name = host[:-len("_host")]
+        if not host.endswith("_host") or name not in nat.SIGNATURES:
+            continue
+        twins += 1
+        assert nat.SIGNATURES[name][0] is res is i, name
+        args = nat.SIGNATURES[name][1]
+        if name == "accv_prepare_images":
+            assert args == host_args and args[-1] is vp, name
+        elif name in workspace:
+            assert args == host_args + [vp, sz, vp], name
+        elif name in threads:
+            assert host_args[-1] is i and args == host_args[:-1] + [vp, sz, vp], name
+        else:
+            assert args == host_args + [vp], name
+    assert twins == 22
+
+
 def test_version_and_error_string():
     from accvlab import _amd_native as nat
 
