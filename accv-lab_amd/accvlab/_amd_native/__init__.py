@@ -83,6 +83,9 @@ RN_MAX_TASKS = 8
 RN_MAX_N = 1024
 RN_MIN_D = 7
 RN_MAX_D = 16
+BD_MAX_K = 1024
+BD_MAX_MAPS = 8
+BD_MAX_EXTRAS = 4
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
@@ -238,6 +241,12 @@ SIGNATURES = {
     "accv_rotated_iou_bev_host": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp]),
     "accv_rotated_nms_bev": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_rotated_nms_bev_host": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+    # 2D box decoding and axis-aligned NMS (params: a BoxDecodeParams / BoxNmsParams by address; outputs [F, M, ...]); their
+    # host entries end in _cpu
+    "accv_box_decode": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_box_decode_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_box_nms": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_box_nms_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -382,6 +391,25 @@ class RotatedNmsParams(ctypes.Structure):
                 ("has_threshold", ctypes.c_int * 8), ("num_tasks", ctypes.c_int)]
 
 
+class BoxDecodeParams(ctypes.Structure):
+    """accv_box_decode_params of include/accv_hip.h"""
+    _fields_ = [("scores", ctypes.c_void_p), ("indices", ctypes.c_void_p), ("classes", ctypes.c_void_p),
+                ("maps", ctypes.c_void_p * 8), ("channels", ctypes.c_int * 8), ("num_maps", ctypes.c_int),
+                ("image_hw_i64", ctypes.c_int), ("image_hw", ctypes.c_void_p), ("image_matrices", ctypes.c_void_p),
+                ("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong), ("score_threshold", ctypes.c_double),
+                ("min_size", ctypes.c_double * 2), ("iou_threshold", ctypes.c_double), ("score_dtype", ctypes.c_int),
+                ("map_dtype", ctypes.c_int), ("has_score_threshold", ctypes.c_int), ("has_min_size", ctypes.c_int),
+                ("has_iou_threshold", ctypes.c_int), ("scores_are_logits", ctypes.c_int), ("clip", ctypes.c_int),
+                ("order_corners", ctypes.c_int), ("class_agnostic", ctypes.c_int)]
+
+
+class BoxNmsParams(ctypes.Structure):
+    """accv_box_nms_params of include/accv_hip.h"""
+    _fields_ = [("boxes", ctypes.c_void_p), ("scores", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+                ("source", ctypes.c_void_p), ("extras", ctypes.c_void_p), ("sizes", ctypes.c_void_p),
+                ("iou_threshold", ctypes.c_double), ("has_threshold", ctypes.c_int), ("class_agnostic", ctypes.c_int)]
+
+
 _lib = None
 _handle = None
 
@@ -397,6 +425,10 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 # interpreter lock for the duration of the call — the trampoline keeps it
 # every host entry runs its whole operator inside the call
 _BLOCKING = {name for name in SIGNATURES if name.endswith("_host")} | {"accv_mtc_async_wait", "accv_mtc_stage_h2d"}
+# accv_X -> its host entry where that is not accv_X_host; these run their whole operator inside the call as well, so they
+# stay on ctypes too
+HOST_ENTRY_NAMES = {"accv_box_decode": "accv_box_decode_cpu", "accv_box_nms": "accv_box_nms_cpu"}
+_CTYPES_ONLY = _BLOCKING | set(HOST_ENTRY_NAMES.values())
 
 
 def _fast_entry(fn, res, args):
@@ -426,7 +458,7 @@ class _Lib:
     def __getattr__(self, name):
         fn = getattr(self._ctypes, name)
         sig = SIGNATURES.get(name)
-        fast = _fast_entry(fn, *sig) if sig and name not in _BLOCKING else None
+        fast = _fast_entry(fn, *sig) if sig and name not in _CTYPES_ONLY else None
         fn = fast or fn
         setattr(self, name, fn)       # cached: __getattr__ is not consulted again
         return fn

@@ -1,6 +1,7 @@
 """How a Python operator hands its operands to the C-ABI: what counts as a ragged operand, that the operands of a call
 share one device, are contiguous and are never copied silently, the argument checks that read the same in every operator,
-and which entry runs — ``accv_X`` on the device's current stream or ``accv_X_host``.
+and which entry runs — ``accv_X`` on the device's current stream or its host entry (``accv_X_host``, or the name the
+operator gives).
 
 Every check takes the operator's name ``who`` for its message.  Checks that one operator words differently stay with that
 operator.  torch is imported on the first check that needs it, so importing this module needs none.
@@ -47,14 +48,15 @@ def number(who, name, v, integer=False):
     return v
 
 
-def run(entry, args, device, who, host_extra=()):
+def run(entry, args, device, who, host_extra=(), host_entry=None):
     """One native call: ``entry`` with torch's current stream of ``device`` behind ``args`` for a CUDA device, else its
-    ``_host`` twin with the tuple ``host_extra`` behind them (what only the host entry takes)."""
+    ``_host`` twin with the tuple ``host_extra`` behind them (what only the host entry takes).  ``host_entry`` names the
+    host entry of an operator whose host entry is not ``entry + "_host"``."""
     if device.type == "cuda":
         with device_guard(device):
             status = getattr(lib(), entry)(*args, stream_ptr(device))
     else:
-        status = getattr(lib(), _HOST_ENTRY[entry])(*(args + host_extra))
+        status = getattr(lib(), host_entry or _HOST_ENTRY[entry])(*(args + host_extra))
     if status != OK:   # check() raises with the library's message; a launch that went well does not pay for the call
         check(status, who)
 

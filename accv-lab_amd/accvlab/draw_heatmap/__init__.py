@@ -28,9 +28,13 @@ visibility-filtered, compacted and cropped annotations and updated projection ma
 Ahead of the 3D target chain: ``bev_augment_boxes`` (the reference's BEVBBoxesTransformer3D, PointsInRangeCheck
 and ConditionalElementRemover: raw ragged 3D boxes and the matrices of their frame -> rotated, scaled and translated boxes,
 range-filtered and compacted, ``BevAugmented``, in one launch; ``bev_augmentation_params`` / ``sample_bev_augmentation``
-build its parameter rows).
+build its parameter rows).  At the end of the 2D path, the inverse of ``boxes_to_heatmap``: ``box_heatmap_decode`` (the peaks of
+the heat map and the offset / size maps of a CenterNet-style camera head -> filtered, IoU-NMS'd, compacted xyxy boxes,
+``BoxDetections``, back in source-image pixels through the matrix of ``prepare_images``, in one launch) and the NMS under it
+as an operator of its own: ``nms_boxes`` (axis-aligned greedy IoU NMS of ragged boxes per frame, class-aware or agnostic).
 """
 from .bev_augment import BevAugmented, bev_augment_boxes, bev_augmentation_params, sample_bev_augmentation
+from .box_decode import BoxDetections, box_heatmap_decode, nms_boxes
 from .box_heatmap import BoxHeatmapTargets, boxes_to_heatmap
 from .camera_boxes import CameraBoxes, camera_augment_boxes
 from .center_decode import CenterPointDetections, center_point_decode
@@ -51,4 +55,4 @@ __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_a
            "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
            "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets",
            "bev_augment_boxes", "BevAugmented", "bev_augmentation_params", "sample_bev_augmentation",
-           "camera_augment_boxes", "CameraBoxes"]
+           "camera_augment_boxes", "CameraBoxes", "box_heatmap_decode", "nms_boxes", "BoxDetections"]

@@ -900,6 +900,89 @@ int accv_rotated_nms_bev_host(const accv_rotated_nms_params* params, long long B
                               long long pre_max_size, long long M, float* boxes, float* scores, long long* labels, int* source,
                               long long* out_sizes);
 
+/* ------------------------------------------------------------------------- 2D box decoding and axis-aligned NMS
+ * The prediction side of a CenterNet / FCOS-style camera head, the inverse of accv_box_heatmap: mmdet's
+ * CenterNetHead._decode_heatmap (models/dense_heads/centernet_head.py: transpose_and_gather_feat of the offset and size
+ * maps at the top-k indices, the corner arithmetic, the rescale to the image) and the NMS behind it (batched_nms of
+ * mmcv/ops/nms.py over torchvision.ops.nms: greedy, iou > threshold suppresses, classes kept apart; without its
+ * coordinate-offset trick, the classes are compared) per frame in ONE launch, without a host round trip.
+ *
+ * accv_box_decode: the peaks scores [F, K] (dtype score_dtype: 0 f32, 1 f16, 2 bf16), indices and classes int64 [F, K] (what
+ * accv_heatmap_peaks writes with per_class == 0), 1 <= K <= ACCV_BD_MAX_K, in rank order; and num_maps (1..ACCV_BD_MAX_MAPS)
+ * maps [F, channels[i], Hm, Wm] contiguous of dtype map_dtype, read in place, whose channels concatenate to 4 + E,
+ * 0 <= E <= ACCV_BD_MAX_EXTRAS: (off_x, off_y, h, w, extras) in map pixels, the layout of accv_box_heatmap's center_offset and
+ * height_width.  The image extent is (image_h, image_w), or row f of image_hw [F, 2] int32 (int64 with image_hw_i64) as
+ * (H, W) when image_hw is not null; clamped to [0, 2^24].  image_matrices: null, or f32 [F, 2, 3], the forward matrix of
+ * accv_prepare_images / accv_camera_boxes.  Per (f, k), in float32 (the operation sequence is written out in
+ * csrc/box_decode_arith.h, nothing contracted):
+ *   legal     0 <= index < Hm * Wm and class >= 0; nothing is read from the maps for an illegal peak
+ *   box       cx = index % Wm + off_x, cy = index / Wm + off_y; corners cx -+ 0.5 * w, cy -+ 0.5 * h; times ux = Wi / Wm and
+ *             uy = Hi / Hm; with clip clamped to [0, Wi] / [0, Hi]
+ *   score     scores[f, k], or 1 / (1 + exp(-scores[f, k])) with scores_are_logits
+ *   valid     legal && (no threshold || score > score_threshold) && (no min_size || (y2 - y1 >= min_size[0] &&
+ *             x2 - x1 >= min_size[1])) && the four corners are finite; NaN fails
+ *   nms       with has_iou_threshold: in rank order a valid peak is kept iff no earlier kept peak (of the same class, unless
+ *             class_agnostic) has iou > iou_threshold with it, strictly; iou = inter / (area_a + area_b - inter); a NaN
+ *             iou suppresses nothing
+ *   written   the first M kept peaks in rank order: the box, with image_matrices its two corners through the inverse of
+ *             the frame's matrix (ordered per axis with order_corners; (0, 0, 0, 0) for a matrix that is singular or not
+ *             finite); the score; the class; source = k; the E extra channels
+ * accv_box_nms: the same NMS on boxes [F, N, 4] f32 xyxy, scores [F, N] f32, labels [F, N] int64, source [F, N] int32,
+ * extras [F, N, E] f32 and sizes [F] int64: what accv_box_decode writes without NMS.  Only the first
+ * n = min(sizes[f], pre_max_size) slots exist, the slot order is the priority order (nothing is sorted), a box with a
+ * coordinate that is not finite is kept and suppresses nothing, without has_threshold every slot is kept; kept rows pass
+ * through bit for bit.  1 <= N <= ACCV_BD_MAX_K, 1 <= M <= min(N, pre_max_size).
+ * Outputs of both, [F, M, ...] contiguous: boxes f32 [.., 4], scores f32, labels int64, source int32, extras f32 [.., E]
+ * (may be null with E == 0), out_sizes int64 [F] (min(kept, M)).  Slots from out_sizes on are written too: +0 everywhere,
+ * source -1 (a complete write).  One workgroup per frame, no atomics, no workspace, no host synchronisation, bitwise
+ * reproducible.  F == 0 launches nothing and writes nothing.  Both return ACCV_EINVAL (null params, negative or oversized
+ * extent, channels that do not add up to 4..8, an unknown dtype, NaN in a threshold or min_size, null or misaligned
+ * pointers) before touching the data, ACCV_ELAUNCH if the launch fails.
+ * accv_box_decode_cpu and accv_box_nms_cpu run the same operation sequence serially on host memory. */
+#define ACCV_BD_MAX_K 1024
+#define ACCV_BD_MAX_MAPS 8
+#define ACCV_BD_MAX_EXTRAS 4
+/* the pointers and scalar parameters of a decode: host memory, read during the call */
+typedef struct accv_box_decode_params {
+    const void* scores;
+    const long long* indices;
+    const long long* classes;
+    const void* maps[ACCV_BD_MAX_MAPS];
+    int channels[ACCV_BD_MAX_MAPS];
+    int num_maps;
+    int image_hw_i64;
+    const void* image_hw;           /* [F, 2] rows (H, W), or null: image_h, image_w for every frame */
+    const float* image_matrices;    /* [F, 2, 3], or null */
+    long long image_h, image_w;
+    double score_threshold;
+    double min_size[2];             /* (h, w) in image pixels */
+    double iou_threshold;
+    int score_dtype, map_dtype;     /* 0 f32, 1 f16, 2 bf16 */
+    int has_score_threshold, has_min_size, has_iou_threshold;
+    int scores_are_logits, clip, order_corners, class_agnostic;
+} accv_box_decode_params;
+/* the inputs and the threshold of an NMS: host memory, read during the call */
+typedef struct accv_box_nms_params {
+    const float* boxes;
+    const float* scores;
+    const long long* labels;
+    const int* source;
+    const float* extras;            /* may be null with E == 0 */
+    const long long* sizes;
+    double iou_threshold;
+    int has_threshold, class_agnostic;
+} accv_box_nms_params;
+int accv_box_decode(const accv_box_decode_params* params, long long F, long long K, long long Hm, long long Wm, long long M,
+                    float* boxes, float* scores, long long* labels, int* source, float* extras, long long* out_sizes,
+                    void* stream);
+int accv_box_decode_cpu(const accv_box_decode_params* params, long long F, long long K, long long Hm, long long Wm, long long M,
+                        float* boxes, float* scores, long long* labels, int* source, float* extras, long long* out_sizes);
+int accv_box_nms(const accv_box_nms_params* params, long long F, long long N, long long E, long long pre_max_size, long long M,
+                 float* boxes, float* scores, long long* labels, int* source, float* extras, long long* out_sizes, void* stream);
+int accv_box_nms_cpu(const accv_box_nms_params* params, long long F, long long N, long long E, long long pre_max_size,
+                     long long M, float* boxes, float* scores, long long* labels, int* source, float* extras,
+                     long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
