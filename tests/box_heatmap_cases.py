@@ -130,6 +130,11 @@ def _oracle(case):
     return out
 
 
+def oracle_of(case):
+    """the oracle of any Case, a drawn one included; not cached by name, read-only"""
+    return _oracle(case)
+
+
 _ORACLES = {}
 
 

@@ -133,7 +133,11 @@ def _colour(v, row, is_bgr):
 @functools.lru_cache(maxsize=None)
 def oracle(name):
     """float64 [B, 3, Hp, Wp] of case `name`; computed once, shared and never written to"""
-    case = cases()[name]
+    return oracle_of(cases()[name])
+
+
+def oracle_of(case):
+    """float64 [B, 3, Hp, Wp] of any Case, a drawn one included; not cached, read-only"""
     B, Hs, Ws = case.images.shape[:3]
     Ho, Wo = case.output_hw or (Hs, Ws)
     kw = case.kw
