@@ -86,6 +86,7 @@ RN_MAX_D = 16
 BD_MAX_K = 1024
 BD_MAX_MAPS = 8
 BD_MAX_EXTRAS = 4
+QD_MAX_K = 1024
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
@@ -247,6 +248,12 @@ SIGNATURES = {
     "accv_box_decode_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_box_nms": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_box_nms_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # top-k box decoding for set-prediction heads (params: a QueryDecode3dParams / QueryDecode2dParams by address; outputs
+    # [B, M, ...]); their host entries end in _cpu
+    "accv_query_decode_3d": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_query_decode_3d_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+    "accv_query_decode_2d": (_i, [_vp, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "accv_query_decode_2d_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -410,6 +417,23 @@ class BoxNmsParams(ctypes.Structure):
                 ("iou_threshold", ctypes.c_double), ("has_threshold", ctypes.c_int), ("class_agnostic", ctypes.c_int)]
 
 
+class QueryDecode3dParams(ctypes.Structure):
+    """accv_query_decode_3d_params of include/accv_hip.h"""
+    _fields_ = [("cls_scores", ctypes.c_void_p), ("bbox_preds", ctypes.c_void_p), ("score_threshold", ctypes.c_double),
+                ("post_center_range", ctypes.c_double * 6), ("score_dtype", ctypes.c_int), ("box_dtype", ctypes.c_int),
+                ("has_score_threshold", ctypes.c_int), ("has_post_center_range", ctypes.c_int),
+                ("scores_are_logits", ctypes.c_int), ("bottom_center", ctypes.c_int)]
+
+
+class QueryDecode2dParams(ctypes.Structure):
+    """accv_query_decode_2d_params of include/accv_hip.h"""
+    _fields_ = [("cls_scores", ctypes.c_void_p), ("bbox_preds", ctypes.c_void_p), ("image_hw", ctypes.c_void_p),
+                ("image_matrices", ctypes.c_void_p), ("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong),
+                ("score_threshold", ctypes.c_double), ("score_dtype", ctypes.c_int), ("box_dtype", ctypes.c_int),
+                ("image_hw_i64", ctypes.c_int), ("has_score_threshold", ctypes.c_int), ("scores_are_logits", ctypes.c_int),
+                ("cxcywh", ctypes.c_int), ("normalized", ctypes.c_int), ("clip", ctypes.c_int), ("order_corners", ctypes.c_int)]
+
+
 _lib = None
 _handle = None
 
@@ -427,7 +451,8 @@ _INT_CLASS = (_vp, _i, _u, _sz, _i64, _ll, _u64)
 _BLOCKING = {name for name in SIGNATURES if name.endswith("_host")} | {"accv_mtc_async_wait", "accv_mtc_stage_h2d"}
 # accv_X -> its host entry where that is not accv_X_host; these run their whole operator inside the call as well, so they
 # stay on ctypes too
-HOST_ENTRY_NAMES = {"accv_box_decode": "accv_box_decode_cpu", "accv_box_nms": "accv_box_nms_cpu"}
+HOST_ENTRY_NAMES = {"accv_box_decode": "accv_box_decode_cpu", "accv_box_nms": "accv_box_nms_cpu",
+                    "accv_query_decode_3d": "accv_query_decode_3d_cpu", "accv_query_decode_2d": "accv_query_decode_2d_cpu"}
 _CTYPES_ONLY = _BLOCKING | set(HOST_ENTRY_NAMES.values())
 
 

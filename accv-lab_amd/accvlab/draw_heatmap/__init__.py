@@ -32,6 +32,10 @@ build its parameter rows).  At the end of the 2D path, the inverse of ``boxes_to
 the heat map and the offset / size maps of a CenterNet-style camera head -> filtered, IoU-NMS'd, compacted xyxy boxes,
 ``BoxDetections``, back in source-image pixels through the matrix of ``prepare_images``, in one launch) and the NMS under it
 as an operator of its own: ``nms_boxes`` (axis-aligned greedy IoU NMS of ragged boxes per frame, class-aware or agnostic).
+For set-prediction heads (DETR, PETR / StreamPETR, BEVFormer), whose loss side lives in ``accvlab.batching_helpers``:
+``query_box_decode_3d`` / ``query_box_decode_2d`` (raw class logits and box rows -> the top ``max_num`` (query, class) pairs
+of every frame in a defined order, decoded, filtered and compacted in one launch, as the ``CenterPointDetections`` /
+``BoxDetections`` that ``rotated_nms_bev`` / ``nms_boxes`` take).
 """
 from .bev_augment import BevAugmented, bev_augment_boxes, bev_augmentation_params, sample_bev_augmentation
 from .box_decode import BoxDetections, box_heatmap_decode, nms_boxes
@@ -45,6 +49,7 @@ from .lanes import (draw_polylines_batched, draw_polylines_multiscale, draw_targ
                     sample_lanes)
 from .ops import draw_heatmap, draw_heatmap_batched, draw_heatmap_multiscale, get_centers_and_radii
 from .peaks import HeatmapPeaks, heatmap_peaks
+from .query_decode import query_box_decode_2d, query_box_decode_3d
 from .rotated_nms import rotated_iou_bev, rotated_nms_bev
 from .visible_boxes import select_visible_bboxes, visible_bbox_mask
 
@@ -55,4 +60,5 @@ __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_a
            "center_point_targets", "CenterPointTargets", "center_point_decode", "CenterPointDetections", "rotated_iou_bev",
            "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets",
            "bev_augment_boxes", "BevAugmented", "bev_augmentation_params", "sample_bev_augmentation",
-           "camera_augment_boxes", "CameraBoxes", "box_heatmap_decode", "nms_boxes", "BoxDetections"]
+           "camera_augment_boxes", "CameraBoxes", "box_heatmap_decode", "nms_boxes", "BoxDetections",
+           "query_box_decode_3d", "query_box_decode_2d"]

@@ -8,12 +8,9 @@
 // NaN: the window maximum carries NaN through as max_pool2d does, so a NaN scores NaN, its finite neighbours are
 // suppressed to ±0 and a suppressed ±inf scores NaN (inf * 0).  torch.sort ranks NaN above +inf.
 //
-// Every element gets a unique 64-bit key: the high word is the order-preserving bit pattern of s (-0.0 folded onto +0.0
-// first, so suppressed negatives tie with real zeros; every NaN mapped to 0xFFFFFFFF, above +inf), the low word
-// 0xFFFFFFFF - index in group.  Larger key = earlier in
-// the output, and since no two keys are equal the top-k of the keys IS the definition: there are no ties left to resolve.
-// Key 0 is never a real key (the low word of a real one is > 0 because group sizes stay below 2^32 - 1): it marks an empty
-// candidate slot.
+// Every element gets a unique 64-bit key (score bits, 0xFFFFFFFF - index in group; topk_select.h, which also holds the
+// radix select and the bitonic sort both launches use): suppressed negatives tie with real zeros, larger key = earlier in
+// the output, and the top-k of the keys IS the definition.
 //
 // Launch 1 (peaks_chunk_kernel): one workgroup per chunk of at most kChunk elements of one plane (R whole rows, or column
 // tiles of kMaxCols columns with their halo for wider maps).  Phase A takes the vertical window maximum of every column
@@ -31,10 +28,12 @@
 
 #include "accv_common.h"
 #include "accv_numeric.h"
+#include "topk_select.h"
 
 namespace {
 
 using namespace accv;   // dtype codes (f64 is not taken here), load / store<DT> with the hardware f16 conversion
+using namespace accv_topk;   // keys, Cut, SelectShared, radix_select, bitonic_sort_desc, kMaxK, kBins, kMaxGroup
 
 constexpr int kThreads = 256;
 constexpr int kPerThread = 16;
@@ -42,14 +41,9 @@ constexpr int kChunk = kThreads * kPerThread;   // interior elements of one chun
 constexpr int kMaxCols = 2048;                  // widest chunk; wider maps are cut into column tiles
 constexpr int kMaxHalf = 3;                     // kernel <= 7
 constexpr int kTileElems = kChunk + 2 * (2 * kMaxHalf);   // R * (chunk columns + halo): 2 rows * (2048 + 6) at most
-constexpr int kMaxK = 1024;
-constexpr int kBins = 256;
 constexpr int kUnroll = 8;                      // candidate keys per lane and step of the group kernel
 constexpr int kGroupThreads = 1024;            // the group kernel: one workgroup per group, 16 waves of candidate loads
 constexpr int kBatch = 4;                       // phase A elements per lane and step
-constexpr long long kMaxGroup = 0xfffffffell;   // 2^32 - 2: the low key word of every real key stays above 0
-
-typedef unsigned long long u64;
 
 struct Geometry {
     long long cw;          // columns of a chunk
@@ -82,94 +76,6 @@ struct Params {
 // max_pool2d's window maximum: a NaN anywhere in the window makes it NaN (fmaxf would skip it).  One v_maximum3_f32
 // per two elements on gfx950, as v_max3_f32 for fmaxf.
 __device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-
-__device__ __forceinline__ unsigned score_bits(float s)
-{
-    if (s != s) return 0xffffffffu;   // every NaN: one key above +inf (torch.sort puts NaN first), read back as NaN
-    unsigned u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;   // -0.0 ranks with +0.0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float score_of(u64 key)
-{
-    const unsigned h = (unsigned)(key >> 32);
-    return __uint_as_float((h & 0x80000000u) ? (h & 0x7fffffffu) : ~h);
-}
-
-// Whether a key is among the selected: all real keys, or those whose top (64 - shift) bits are >= prefix.
-struct Cut {
-    u64 prefix;
-    int shift;   // 64: take every real key
-    __device__ bool take(u64 key) const { return key != 0 && (shift >= 64 || (key >> shift) >= prefix); }
-};
-
-struct SelectShared {
-    unsigned hist[kBins];
-    unsigned bin, above, count;
-    unsigned slots;   // next free output slot
-};
-
-// histogram add; every lane of the wave must call it (the wave's lanes that share the leading lane's digit add once:
-// heat maps are mostly suppressed zeros, which would otherwise all hit one bin)
-__device__ __forceinline__ void hist_add(unsigned* hist, bool active, unsigned digit)
-{
-    const u64 act = __ballot(active);
-    if (act == 0) return;
-    const int leader = __ffsll((long long)act) - 1;
-    const unsigned lead_digit = __shfl(digit, leader);
-    const bool same = active && digit == lead_digit;
-    const u64 same_mask = __ballot(same);
-    if (same) {
-        if ((int)__lane_id() == leader) atomicAdd(&hist[lead_digit], (unsigned)__popcll(same_mask));
-    } else if (active) {
-        atomicAdd(&hist[digit], 1u);
-    }
-}
-
-// MSB-first radix select of the k-th largest real key among those every lane visits with for_each(f).  Returns the cut
-// that keeps exactly k keys.  Needs at least k real keys.  Every thread of the block calls it.
-template <class ForEach>
-__device__ Cut radix_select(ForEach for_each, unsigned k, SelectShared& sh)
-{
-    const int tid = threadIdx.x;
-    u64 prefix = 0;
-    unsigned krem = k;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        for (int i = tid; i < kBins; i += blockDim.x) sh.hist[i] = 0;
-        __syncthreads();
-        for_each([&](u64 key) {
-            const bool active = key != 0 && (shift == 56 || (key >> (shift + 8)) == prefix);
-            hist_add(sh.hist, active, (unsigned)(key >> shift) & 0xffu);
-        });
-        __syncthreads();
-        if (tid < 64) {
-            // lane l holds bins 255 - 4l .. 252 - 4l; an inclusive scan from the top bin down finds the k-th key's bin
-            unsigned h[4], sum = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = sh.hist[255 - 4 * tid - j], sum += h[j];
-            unsigned incl = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned v = __shfl_up(incl, d);
-                if (tid >= d) incl += v;
-            }
-            unsigned before = incl - sum;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (before < krem && krem <= before + h[j]) sh.bin = 255 - 4 * tid - j, sh.above = before, sh.count = h[j];
-                before += h[j];
-            }
-        }
-        __syncthreads();
-        const unsigned bin = sh.bin, above = sh.above, count = sh.count;
-        prefix = (prefix << 8) | bin;
-        krem -= above;
-        if (count == krem) return Cut{prefix, shift};
-        __syncthreads();   // sh.bin is rewritten by the next pass
-    }
-    return Cut{prefix, 0};   // not reached: keys are unique, so the last digit's bin holds exactly one key
-}
 
 template <int DT, int HALF>
 __global__ __launch_bounds__(kThreads) void peaks_chunk_kernel(const void* __restrict__ x, Params p, u64* __restrict__ ws)
@@ -299,18 +205,7 @@ __global__ __launch_bounds__(kGroupThreads) void peaks_group_kernel(const u64* _
     });
     __syncthreads();
 
-    // bitonic sort, descending
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < P / 2; t += kGroupThreads) {
-                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const bool desc = (i & size) == 0;
-                const u64 a = s_sel[i], b = s_sel[j];
-                if ((a < b) == desc) s_sel[i] = b, s_sel[j] = a;
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_desc<kGroupThreads>(s_sel, P);
 
     const long long hw = p.H * p.W;
     for (int i = tid; i < (int)k; i += kGroupThreads) {

@@ -983,6 +983,69 @@ int accv_box_nms_cpu(const accv_box_nms_params* params, long long F, long long N
                      long long M, float* boxes, float* scores, long long* labels, int* source, float* extras,
                      long long* out_sizes);
 
+/* ------------------------------------------------------------------------- top-k box decoding for set-prediction heads
+ * The prediction side of a DETR-style head (DETR, Deformable DETR, DINO, PETR / StreamPETR, BEVFormer, DETR3D): mmdet3d's
+ * NMSFreeCoder.decode with denormalize_bbox (core/bbox/coders/nms_free_coder.py: sigmoid over all logits, topk over Q * C,
+ * div and mod, gather, the element-wise decode, two masks, a boolean index per frame) and mmdet's
+ * DETRHead._predict_by_feat_single, per frame in ONE launch, without a host round trip and in a defined order.
+ *
+ * cls_scores [B, Q, C] (dtype score_dtype: 0 f32, 1 f16, 2 bf16) and bbox_preds [B, Q, D] (dtype box_dtype), contiguous,
+ * read in place.  1 <= M = max_num <= ACCV_QD_MAX_K, M <= Q * C, Q * C < 2^32 - 1.  Per frame (the operation sequence is
+ * written out in csrc/query_decode_arith.h, nothing contracted):
+ *   select    the M first of the Q * C raw values ranked by descending value, equal values (-0.0 == +0.0) by ascending flat
+ *             index q * C + c, every NaN above +inf: torch.sort(descending, stable)[:M], the order of accv_heatmap_peaks;
+ *             q = index / C, label = index % C
+ *   score     the raw value, or 1 / (1 + exp(-value)) with scores_are_logits
+ *   3d row    D = 8 or 10, (cx, cy, log w, log l, cz, log h, sin, cos[, vx, vy]) -> (cx, cy, cz, exp w, exp l, exp h,
+ *             atan2(sin, cos)[, vx, vy]), D - 1 values; valid iff (no threshold || score > score_threshold) && (no range ||
+ *             post_center_range[0:3] <= (cx, cy, cz) <= post_center_range[3:6]); with bottom_center the written z is
+ *             cz - exp h * 0.5, after the range test
+ *   2d row    D = 4; cxcywh: (cx -+ 0.5 * w, cy -+ 0.5 * h), else xyxy as it is; with normalized x * Wi, y * Hi; with clip
+ *             clamped to [0, Wi] / [0, Hi]; valid iff (no threshold || score > score_threshold) && the four coordinates are
+ *             finite; with image_matrices the written corners go through the inverse of the frame's matrix as in
+ *             accv_box_decode (ordered per axis with order_corners; (0, 0, 0, 0) for a matrix that is singular or not
+ *             finite).  The image extent is (image_h, image_w), or row b of image_hw [B, 2] int32 (int64 with
+ *             image_hw_i64) as (H, W) when image_hw is not null; clamped to [0, 2^24]
+ *   written   the valid ranks in rank order; source = q.  NaN fails every comparison
+ * Outputs, [B, M, ...] contiguous: boxes f32 [.., D - 1] (3d) or [.., 4] (2d), scores f32, labels int64, source int32,
+ * out_sizes int64 [B].  Slots from out_sizes on are written too: +0 everywhere, source -1 (a complete write).  One
+ * workgroup per frame, no atomics on global memory, no workspace, no host synchronisation, bitwise reproducible.  B == 0
+ * launches nothing and writes nothing.  Both return ACCV_EINVAL (null params, negative or oversized extent, a D other than
+ * 8 / 10, an unknown dtype, NaN in a threshold or range, null or misaligned pointers) before touching the data,
+ * ACCV_ELAUNCH if the launch fails.
+ * accv_query_decode_3d_cpu and accv_query_decode_2d_cpu run the same operation sequence serially on host memory (the
+ * selection as a stable sort on the same keys). */
+#define ACCV_QD_MAX_K 1024
+/* the pointers and scalar parameters of a decode: host memory, read during the call */
+typedef struct accv_query_decode_3d_params {
+    const void* cls_scores;
+    const void* bbox_preds;
+    double score_threshold;
+    double post_center_range[6];    /* (x0, y0, z0, x1, y1, z1) */
+    int score_dtype, box_dtype;     /* 0 f32, 1 f16, 2 bf16 */
+    int has_score_threshold, has_post_center_range;
+    int scores_are_logits, bottom_center;
+} accv_query_decode_3d_params;
+typedef struct accv_query_decode_2d_params {
+    const void* cls_scores;
+    const void* bbox_preds;
+    const void* image_hw;           /* [B, 2] rows (H, W), or null: image_h, image_w for every frame */
+    const float* image_matrices;    /* [B, 2, 3], or null */
+    long long image_h, image_w;
+    double score_threshold;
+    int score_dtype, box_dtype;     /* 0 f32, 1 f16, 2 bf16 */
+    int image_hw_i64, has_score_threshold;
+    int scores_are_logits, cxcywh, normalized, clip, order_corners;
+} accv_query_decode_2d_params;
+int accv_query_decode_3d(const accv_query_decode_3d_params* params, long long B, long long Q, long long C, long long D, long long M,
+                         float* boxes, float* scores, long long* labels, int* source, long long* out_sizes, void* stream);
+int accv_query_decode_3d_cpu(const accv_query_decode_3d_params* params, long long B, long long Q, long long C, long long D,
+                             long long M, float* boxes, float* scores, long long* labels, int* source, long long* out_sizes);
+int accv_query_decode_2d(const accv_query_decode_2d_params* params, long long B, long long Q, long long C, long long M, float* boxes,
+                         float* scores, long long* labels, int* source, long long* out_sizes, void* stream);
+int accv_query_decode_2d_cpu(const accv_query_decode_2d_params* params, long long B, long long Q, long long C, long long M,
+                             float* boxes, float* scores, long long* labels, int* source, long long* out_sizes);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
