@@ -87,6 +87,9 @@ BD_MAX_K = 1024
 BD_MAX_MAPS = 8
 BD_MAX_EXTRAS = 4
 QD_MAX_K = 1024
+DT_MAX_CAMERAS = 16
+DT_BAND_CELLS = 8192
+DT_MAX_BINS = 32768
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
@@ -254,6 +257,9 @@ SIGNATURES = {
     "accv_query_decode_3d_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
     "accv_query_decode_2d": (_i, [_vp, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "accv_query_decode_2d_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+    # lidar depth targets (params: a DepthTargetsParams by address; outputs [B, C, h, w]); the host entry ends in _cpu
+    "accv_depth_targets": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
+    "accv_depth_targets_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -434,6 +440,15 @@ class QueryDecode2dParams(ctypes.Structure):
                 ("cxcywh", ctypes.c_int), ("normalized", ctypes.c_int), ("clip", ctypes.c_int), ("order_corners", ctypes.c_int)]
 
 
+class DepthTargetsParams(ctypes.Structure):
+    """accv_depth_targets_params of include/accv_hip.h"""
+    _fields_ = [("points", ctypes.c_void_p), ("sample_sizes", ctypes.c_void_p), ("projection", ctypes.c_void_p),
+                ("image_transforms", ctypes.c_void_p), ("image_h", ctypes.c_longlong), ("image_w", ctypes.c_longlong),
+                ("depth_min", ctypes.c_double), ("depth_max", ctypes.c_double), ("bin_lo", ctypes.c_double),
+                ("bin_step", ctypes.c_double), ("downsample", ctypes.c_int), ("bin_count", ctypes.c_int),
+                ("sizes_i64", ctypes.c_int), ("band_rows", ctypes.c_int)]
+
+
 _lib = None
 _handle = None
 
@@ -452,7 +467,8 @@ _BLOCKING = {name for name in SIGNATURES if name.endswith("_host")} | {"accv_mtc
 # accv_X -> its host entry where that is not accv_X_host; these run their whole operator inside the call as well, so they
 # stay on ctypes too
 HOST_ENTRY_NAMES = {"accv_box_decode": "accv_box_decode_cpu", "accv_box_nms": "accv_box_nms_cpu",
-                    "accv_query_decode_3d": "accv_query_decode_3d_cpu", "accv_query_decode_2d": "accv_query_decode_2d_cpu"}
+                    "accv_query_decode_3d": "accv_query_decode_3d_cpu", "accv_query_decode_2d": "accv_query_decode_2d_cpu",
+                    "accv_depth_targets": "accv_depth_targets_cpu"}
 _CTYPES_ONLY = _BLOCKING | set(HOST_ENTRY_NAMES.values())
 
 

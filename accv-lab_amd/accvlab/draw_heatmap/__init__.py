@@ -36,6 +36,10 @@ For set-prediction heads (DETR, PETR / StreamPETR, BEVFormer), whose loss side l
 ``query_box_decode_3d`` / ``query_box_decode_2d`` (raw class logits and box rows -> the top ``max_num`` (query, class) pairs
 of every frame in a defined order, decoded, filtered and compacted in one launch, as the ``CenterPointDetections`` /
 ``BoxDetections`` that ``rotated_nms_bev`` / ``nms_boxes`` take).
+
+For the depth supervision of LSS heads (BEVDepth, BEVDet4D-Depth, BEVStereo): ``lidar_depth_targets`` (the lidar points of
+a frame -> the nearest depth and its bin per cell of every camera's downsampled feature map, through the image matrix
+``prepare_images`` warped the image with, in one launch).
 """
 from .bev_augment import BevAugmented, bev_augment_boxes, bev_augmentation_params, sample_bev_augmentation
 from .box_decode import BoxDetections, box_heatmap_decode, nms_boxes
@@ -44,6 +48,7 @@ from .camera_boxes import CameraBoxes, camera_augment_boxes
 from .center_decode import CenterPointDetections, center_point_decode
 from .center_regression import center_regression_loss, gather_at_centers
 from .center_targets import CenterPointTargets, center_point_targets
+from .depth_targets import DepthTargets, lidar_depth_targets
 from .focal_loss import gaussian_focal_loss
 from .lanes import (draw_polylines_batched, draw_polylines_multiscale, draw_targets_multiscale, sample_lane_targets,
                     sample_lanes)
@@ -61,4 +66,4 @@ __all__ = ["__version__", "draw_heatmap", "draw_heatmap_batched", "get_centers_a
            "rotated_nms_bev", "visible_bbox_mask", "select_visible_bboxes", "boxes_to_heatmap", "BoxHeatmapTargets",
            "bev_augment_boxes", "BevAugmented", "bev_augmentation_params", "sample_bev_augmentation",
            "camera_augment_boxes", "CameraBoxes", "box_heatmap_decode", "nms_boxes", "BoxDetections",
-           "query_box_decode_3d", "query_box_decode_2d"]
+           "query_box_decode_3d", "query_box_decode_2d", "lidar_depth_targets", "DepthTargets"]

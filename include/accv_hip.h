@@ -1046,6 +1046,54 @@ int accv_query_decode_2d(const accv_query_decode_2d_params* params, long long B,
 int accv_query_decode_2d_cpu(const accv_query_decode_2d_params* params, long long B, long long Q, long long C, long long M,
                              float* boxes, float* scores, long long* labels, int* source, long long* out_sizes);
 
+/* --------------------------------------------------------------------------------------------- lidar depth targets
+ * The depth supervision of an LSS head (BEVDepth, BEVDet4D-Depth, BEVStereo) in ONE launch: replaces the loader's
+ * per-camera CPU pass (BEVDepth's map_pointcloud_to_image and depth_transform: numpy matmul, mask, a scatter into a
+ * full-resolution H x W map) and the head's device pass over [B, N, H, W] (get_downsampled_gt_depth: reshape, min over
+ * stride x stride blocks, bin index, one-hot).
+ *
+ * points [B, P, D] f32, D >= 3, contiguous: channels 0..2 are x, y, z, the rest is never read; sample_sizes [B] int32
+ * (int64 with sizes_i64), clamped to [0, P], slots from it on are never read.  projection [B, C, R, 4] f32, R = 3 or 4,
+ * 1 <= C <= ACCV_DT_MAX_CAMERAS, lidar to image pixels; row 3 is never read.  image_transforms [B, C, 2, 3] f32 or null: the
+ * forward image matrix, folded into rows 0 and 1 exactly as accv_camera_boxes writes its projection matrices.
+ * 1 <= image_h, image_w <= 2^24, downsample >= 1; the maps are h x w = ceil(image_h / downsample) x ceil(image_w / downsample),
+ * w <= ACCV_DT_BAND_CELLS.  0 < depth_min < depth_max, finite.  bin_count = 0: no bins (bins may be null); else
+ * 1 <= bin_count <= ACCV_DT_MAX_BINS, bin_step > 0, bin_lo and bin_step finite.  The scalars are rounded to float32 once.
+ * Per (b, c) and real point, in float32 (csrc/depth_targets_arith.h, nothing contracted):
+ *   p_k = ((m_k0*x + m_k1*y) + m_k2*z) + m_k3, k = 0, 1, 2;  d = p_2, u = p_0 / d, v = p_1 / d
+ *   the point counts iff d >= depth_min && d < depth_max && u >= 0 && u < image_w && v >= 0 && v < image_h (NaN fails)
+ *   its cell is (int(v) / downsample, int(u) / downsample)
+ *   depth[b, c, cy, cx] = the smallest d of the cell, +0 where there is none
+ *   bins[b, c, cy, cx]  = int(t), t = (depth - bin_lo) / bin_step, if the cell has a point, t >= 0 and int(t) < bin_count;
+ *                         else -1
+ * Outputs depth f32 and bins int32, [B, C, h, w] contiguous, every element written exactly once.  Output-stationary: the
+ * map of a (b, c) is cut into bands of band_rows whole rows (0: chosen by the library; band_rows * w <=
+ * ACCV_DT_BAND_CELLS), the grid is (bands, C, B), B <= 65535; a workgroup keeps its band in LDS, streams the frame's points
+ * and takes an LDS atomic minimum on the bit pattern of d.  No atomics on global memory, no workspace, no clear, no host
+ * synchronisation; the minimum does not depend on the order, so the result is bitwise reproducible and the same for every
+ * band_rows.  B == 0 launches nothing and writes nothing; P == 0 writes +0 and -1.  ACCV_EINVAL (null params, a size or
+ * scalar outside the ranges above, null or misaligned pointers) before touching the data, ACCV_ELAUNCH if the launch fails.
+ * accv_depth_targets_cpu runs the same operation sequence serially on host memory. */
+#define ACCV_DT_MAX_CAMERAS 16
+#define ACCV_DT_BAND_CELLS 8192
+#define ACCV_DT_MAX_BINS 32768
+/* the inputs and scalar parameters of a call: host memory, read during the call */
+typedef struct accv_depth_targets_params {
+    const float* points;
+    const void* sample_sizes;
+    const float* projection;
+    const float* image_transforms;  /* or null */
+    long long image_h, image_w;
+    double depth_min, depth_max;
+    double bin_lo, bin_step;
+    int downsample, bin_count;      /* bin_count 0: no bins */
+    int sizes_i64, band_rows;       /* band_rows 0: automatic */
+} accv_depth_targets_params;
+int accv_depth_targets(const accv_depth_targets_params* params, long long B, long long P, long long D, long long C, long long R,
+                       float* depth, int* bins, void* stream);
+int accv_depth_targets_cpu(const accv_depth_targets_params* params, long long B, long long P, long long D, long long C,
+                           long long R, float* depth, int* bins);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
