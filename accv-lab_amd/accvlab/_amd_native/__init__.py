@@ -90,6 +90,10 @@ QD_MAX_K = 1024
 DT_MAX_CAMERAS = 16
 DT_BAND_CELLS = 8192
 DT_MAX_BINS = 32768
+VX_MIN_D = 3
+VX_MAX_D = 16
+VX_MAX_POINTS = 128
+VX_MAX_VOXELS = 1 << 20
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
@@ -260,6 +264,11 @@ SIGNATURES = {
     # lidar depth targets (params: a DepthTargetsParams by address; outputs [B, C, h, w]); the host entry ends in _cpu
     "accv_depth_targets": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
     "accv_depth_targets_cpu": (_i, [_vp, _ll, _ll, _ll, _ll, _ll, _vp, _vp]),
+    # hard voxelization (params: a VoxelizeParams by address; outputs [B, V, ...] and point_voxel [B, P]); the host entry ends
+    # in _cpu and takes no workspace
+    "accv_voxelize_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll, _ll]),
+    "accv_voxelize": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "accv_voxelize_cpu": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -449,6 +458,14 @@ class DepthTargetsParams(ctypes.Structure):
                 ("sizes_i64", ctypes.c_int), ("band_rows", ctypes.c_int)]
 
 
+class VoxelizeParams(ctypes.Structure):
+    """accv_voxelize_params of include/accv_hip.h"""
+    _fields_ = [("points", ctypes.c_void_p), ("sample_sizes", ctypes.c_void_p), ("augmentation", ctypes.c_void_p),
+                ("voxel_size", ctypes.c_double * 3), ("range_min", ctypes.c_double * 3), ("range_max", ctypes.c_double * 3),
+                ("table_slots", ctypes.c_longlong), ("max_points", ctypes.c_int), ("max_voxels", ctypes.c_int),
+                ("sizes_i64", ctypes.c_int)]
+
+
 _lib = None
 _handle = None
 
@@ -468,7 +485,7 @@ _BLOCKING = {name for name in SIGNATURES if name.endswith("_host")} | {"accv_mtc
 # stay on ctypes too
 HOST_ENTRY_NAMES = {"accv_box_decode": "accv_box_decode_cpu", "accv_box_nms": "accv_box_nms_cpu",
                     "accv_query_decode_3d": "accv_query_decode_3d_cpu", "accv_query_decode_2d": "accv_query_decode_2d_cpu",
-                    "accv_depth_targets": "accv_depth_targets_cpu"}
+                    "accv_depth_targets": "accv_depth_targets_cpu", "accv_voxelize": "accv_voxelize_cpu"}
 _CTYPES_ONLY = _BLOCKING | set(HOST_ENTRY_NAMES.values())
 
 

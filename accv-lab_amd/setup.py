@@ -25,7 +25,7 @@ setup(
     name="accvlab-amd",
     version="0.1.0",
     description="MI355X-native (gfx950, hand-written HIP) drop-in for ACCV-Lab's draw_heatmap / batching_helpers / "
-                "multi_tensor_copier / lane_helpers",
+                "multi_tensor_copier / lane_helpers, with the image_prep and point_cloud extensions",
     packages=find_namespace_packages(where=HERE, include=["accvlab", "accvlab.*"]),
     package_dir={"": "."},
     package_data={"accvlab._amd_native": ["*.so"], "accvlab.multi_tensor_copier": ["*.so"],

@@ -1094,6 +1094,58 @@ int accv_depth_targets(const accv_depth_targets_params* params, long long B, lon
 int accv_depth_targets_cpu(const accv_depth_targets_params* params, long long B, long long P, long long D, long long C,
                            long long R, float* depth, int* bins);
 
+/* ------------------------------------------------------------------------------------------------- hard voxelization
+ * The pass from the lidar points of a batch of frames to the voxels or pillars the network reads: replaces mmcv's
+ * Voxelization (hard_voxelize_forward; spconv's points_to_voxel is the same rule), which mmdet3d calls once per frame in a
+ * Python loop (Base3DDetector.voxelize) and whose GPU kernel hands out voxel numbers with an atomic counter.  The result
+ * here is the one of the SEQUENTIAL loop (hard_voxelize_forward_cpu), bit for bit, on the device and on the host.
+ *
+ * points [B, P, D] f32, ACCV_VX_MIN_D <= D <= ACCV_VX_MAX_D, contiguous: channels 0..2 are x, y, z, the rest passes through;
+ * sample_sizes [B] int32 (int64 with sizes_i64), clamped to [0, P], slots from it on are never read.  augmentation
+ * [B, 7] f32 or null: the rows (θ, c, s, k, tx, ty, tz) of accv_bev_augment; x, y, z go through its augment_center before
+ * the voxel test and are stored augmented.  voxel_size (vx, vy, vz) > 0, range_min < range_max, all finite, rounded to
+ * float32 once; the grid is g_k = rint((hi_k - lo_k) / v_k) in float32, each g_k >= 1, g_x * g_y * g_z < 2^31.
+ * 1 <= max_points = T <= ACCV_VX_MAX_POINTS, 1 <= max_voxels = V <= ACCV_VX_MAX_VOXELS, B <= 65535, P < 2^31 - 1.
+ * Per frame, points in slot order, float32, nothing contracted (csrc/voxelize_arith.h):
+ *   t_k = floor((p_k - lo_k) / v_k); in range iff t_k >= 0 && t_k < (float)g_k for k = x, y, z (float compares: NaN, +inf and
+ *   -inf fail; mmcv casts first);  c_k = (int)t_k,  key = (c_z * g_y + c_y) * g_x + c_x
+ *   a key without a voxel: with V voxels open the point is skipped AND THE LOOP GOES ON (mmcv's `continue`, not the older
+ *   `break`); else the voxel takes the next number and coors = (c_z, c_y, c_x)
+ *   a voxel with fewer than T points stores the point's D channels in its next row (x, y, z augmented, the rest bit for bit)
+ * Outputs, every element written exactly once: voxels f32 [B, V, T, D] (+0 rows from num_points on and in voxels from
+ * voxel_counts on), coors int32 [B, V, 3] (-1 from voxel_counts on), num_points int32 [B, V] (0 from voxel_counts on),
+ * voxel_counts int32 [B], point_voxel int32 [B, P] or null (the voxel number of each point, also of a point beyond T; -1 out
+ * of range, beyond sample_sizes or refused by V).
+ * Device: one hipMemsetAsync and five launches on `stream` (insert and rank: a lane per point; count and number: a
+ * workgroup per chunk of 4096 points of a frame, further workgroups of count fill the index lists; gather: a lane per 16 or
+ * 4 bytes of voxels; three launches when P == 0), no host synchronisation, capturable.  No atomic decides an order: a per-frame hash table (table_slots slots, 0 = the power of
+ * two that is at least 2 * P; else a power of two above P, at most 2^31) keeps the lowest point index per key, a prefix sum
+ * over the points numbers the voxels, and a bounded atomicMin cascade sorts each voxel's first T indices.  workspace:
+ * accv_voxelize_workspace_bytes(B, P, V, T, table_slots) bytes of device memory, 16-byte aligned (0 for sizes the call
+ * refuses).  B == 0 launches nothing; P == 0 still writes all padding.  ACCV_EINVAL (null params, a size or scalar outside
+ * the ranges above, null or misaligned pointers) or ACCV_EWORKSPACE before touching the data, ACCV_ELAUNCH if a launch
+ * fails.  accv_voxelize_cpu runs the sequential loop over the same arithmetic on host memory and needs no workspace. */
+#define ACCV_VX_MIN_D 3
+#define ACCV_VX_MAX_D 16
+#define ACCV_VX_MAX_POINTS 128
+#define ACCV_VX_MAX_VOXELS 1048576
+/* the inputs and scalar parameters of a call: host memory, read during the call */
+typedef struct accv_voxelize_params {
+    const float* points;
+    const void* sample_sizes;
+    const float* augmentation;      /* or null */
+    double voxel_size[3];           /* x, y, z */
+    double range_min[3], range_max[3];
+    long long table_slots;          /* 0: automatic */
+    int max_points, max_voxels;
+    int sizes_i64;
+} accv_voxelize_params;
+size_t accv_voxelize_workspace_bytes(long long B, long long P, long long V, long long T, long long table_slots);
+int accv_voxelize(const accv_voxelize_params* params, long long B, long long P, long long D, float* voxels, int* coors,
+                  int* num_points, int* voxel_counts, int* point_voxel, void* workspace, size_t workspace_bytes, void* stream);
+int accv_voxelize_cpu(const accv_voxelize_params* params, long long B, long long P, long long D, float* voxels, int* coors,
+                      int* num_points, int* voxel_counts, int* point_voxel);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy

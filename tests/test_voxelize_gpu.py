@@ -1,0 +1,121 @@
+"""voxelize_points on the GPU: the five kernels against the numpy float32 restatement of the sequential loop in
+voxelize_cases.py and against the host entry on the same inputs, bit for bit on all five outputs — the cases of
+test_voxelize_cpu.py on the device, the edges of the kernels' work partition (a lane per point in workgroups of kThreads; the
+counting and numbering workgroups' chunk of kScanThreads * kUnroll points), the hash table at its smallest legal size, guard
+bands around every output and the workspace through the C entry alone, a non-default stream, a hipGraph capture and replay,
+errors before any launch and empty inputs."""
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import voxelize_cases as cases  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+_SRC = open(os.path.join(ROOT, "accv-lab_amd", "csrc", "voxelize.hip")).read()
+THREADS, SCAN_THREADS, UNROLL = (int(re.search(rf"constexpr int {name} = (\d+);", _SRC).group(1))
+                                 for name in ("kThreads", "kScanThreads", "kUnroll"))
+assert (THREADS, SCAN_THREADS, UNROLL) == (256, 1024, 4)
+
+
+@pytest.mark.parametrize("B,D,size_dtype,grid,T,V,below", cases.CONFIGS)
+def test_random_configurations_against_the_definition(B, D, size_dtype, grid, T, V, below):
+    cases.check_config(DEV, B, D, size_dtype, grid, T, V, below)
+
+
+def test_work_partition_edges_and_table_size_rule():
+    cases.check_partition(DEV, THREADS, SCAN_THREADS * UNROLL)
+
+
+def test_gpu_against_cpu_tensors():
+    """the same call on CPU tensors gives the same bits, with and without rows, for 16-byte and 4-byte rows"""
+    sizes = (SCAN_THREADS * UNROLL + 1, 0, THREADS + 1)
+    for D in (4, 7):
+        pts = cases.random_points(70 + D, sizes, D)
+        for aug in (None, cases.rows(D, 3)):
+            kw = dict(max_points=5, max_voxels=200, augmentation=aug, **cases.VOXELS3D)
+            cases.check_equal(cases.run(pts, sizes, DEV, **kw), cases.run(pts, sizes, "cpu", **kw), f"D {D}")
+
+
+def test_truncation_by_max_points_and_max_voxels_follows_the_continue_rule():
+    cases.check_truncation(DEV)
+
+
+def test_table_sizes_two_calls_and_untouched_inputs():
+    cases.check_table_pressure(DEV)
+
+
+def test_hand_placed_points_at_every_edge_of_the_definition():
+    cases.check_hand_placed(DEV)
+
+
+def test_augmentation_rows_equal_augmented_points():
+    cases.check_augmentation(DEV)
+
+
+def test_concatenate_voxels_against_slice_and_cat():
+    cases.check_concatenate(DEV)
+
+
+def test_points_off_a_16_byte_boundary():
+    cases.misaligned_points(DEV)
+
+
+def test_no_frames_no_points_and_sizes_of_zero():
+    cases.check_empty(DEV)
+
+
+def test_guard_bands_workspace_and_complete_write_through_the_c_entry_alone():
+    cases.check_guard_bands(DEV)
+
+
+def test_every_documented_error_is_raised_before_a_launch():
+    cases.check_errors(DEV, other_dev="cpu")
+
+
+def _stream_case():
+    sizes = (1500, 257)
+    pts = cases.random_points(81, sizes, 4)
+    kw = dict(max_points=3, max_voxels=150, **cases.VOXELS3D)
+    return pts, sizes, cases.rows(8, 2), kw
+
+
+def test_runs_on_the_current_stream():
+    """the memset and the launches go to torch's current stream: on a side stream, after work that stream alone waits for"""
+    pts, sizes, rows, kw = _stream_case()
+    want = cases.definition(pts, sizes, augmentation=rows, **kw)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        rb = cases.ragged(cases.np.zeros_like(pts), sizes, DEV)
+        rb.tensor.copy_(torch.from_numpy(pts).to(DEV))       # enqueued on the side stream (a copy keeps the NaN payloads); the
+        #                                                      operator must follow it there
+        got = cases.voxelize_points(rb, augmentation=torch.from_numpy(rows).to(DEV), return_point_voxel=True, **kw)
+    side.synchronize()
+    cases.check_equal(got, want, "side stream")
+
+
+def test_graph_capture_and_replay_give_the_bits_of_the_eager_call():
+    """one linear chain: the memset node and the five kernel nodes; the replay runs on new points in the captured tensor"""
+    pts, sizes, rows, kw = _stream_case()
+    rb, aug = cases.ragged(pts, sizes, DEV), torch.from_numpy(rows).to(DEV)
+    eager = cases.voxelize_points(rb, augmentation=aug, return_point_voxel=True, **kw)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = cases.voxelize_points(rb, augmentation=aug, return_point_voxel=True, **kw)
+    other = cases.random_points(82, sizes, 4)
+    rb.tensor.copy_(torch.from_numpy(other))
+    graph.replay()
+    torch.cuda.synchronize()
+    cases.check_equal(captured, cases.definition(other, sizes, augmentation=rows, **kw), "replay on new points")
+    rb.tensor.copy_(torch.from_numpy(pts))
+    graph.replay()
+    torch.cuda.synchronize()
+    cases.check_equal(captured, eager, "replay")
