@@ -19,6 +19,7 @@ import torch
 from .. import _amd_native as _nat
 from .._amd_native import operands as _ops
 from ..batching_helpers import RaggedBatch
+from . import _detections as _det
 
 MAX_K = _nat.BD_MAX_K
 MAX_MAPS = _nat.BD_MAX_MAPS
@@ -37,81 +38,8 @@ class BoxDetections(NamedTuple):
     extras: object   # float32 [F, M, E]
 
 
-def _check_peaks(p):
-    """scores, indices, classes after every check"""
-    if not all(hasattr(p, n) for n in ("scores", "indices", "classes")):
-        raise RuntimeError(f"{_DEC}: peaks must be a HeatmapPeaks (scores, indices, classes)")
-    s, i, c = p.scores, p.indices, p.classes
-    for name, x in (("scores", s), ("indices", i), ("classes", c)):
-        if not isinstance(x, torch.Tensor):
-            raise RuntimeError(f"{_DEC}: peaks.{name} must be a tensor")
-        if x.dim() != 2:
-            raise RuntimeError(f"{_DEC}: peaks.{name} must be [F, K] (heatmap_peaks with per_class=False), got {tuple(x.shape)}")
-        if not x.is_contiguous():
-            raise RuntimeError(f"{_DEC}: peaks.{name} must be contiguous (it is not copied silently)")
-    _ops.check_backend(_DEC, "peaks", s.device)
-    if s.dtype not in _DTYPES or s.dtype == torch.float64:
-        raise RuntimeError(f"{_DEC}: peaks.scores must be float32, float16 or bfloat16, got {s.dtype}")
-    if not 1 <= s.shape[1] <= MAX_K:
-        raise RuntimeError(f"{_DEC}: K must be in 1..{MAX_K}, got {s.shape[1]}")
-    for name, x in (("indices", i), ("classes", c)):
-        if x.dtype != torch.int64 or x.shape != s.shape or x.device != s.device:
-            raise RuntimeError(f"{_DEC}: peaks.{name} must be int64 {tuple(s.shape)} on {s.device}, got {x.dtype} "
-                               f"{tuple(x.shape)} on {x.device}")
-    return s, i, c
-
-
-def _check_feats(feats, scores):
-    """the maps as a tuple after every check"""
-    maps = (feats,) if isinstance(feats, torch.Tensor) else tuple(feats) if isinstance(feats, (list, tuple)) else None
-    if not maps:
-        raise RuntimeError(f"{_DEC}: feats must be a tensor or a non-empty sequence of tensors")
-    if len(maps) > MAX_MAPS:
-        raise RuntimeError(f"{_DEC}: at most {MAX_MAPS} maps are supported, feats has {len(maps)}")
-    for i, m in enumerate(maps):
-        if not isinstance(m, torch.Tensor):
-            raise RuntimeError(f"{_DEC}: feats[{i}] must be a tensor")
-        if m.dim() != 4:
-            raise RuntimeError(f"{_DEC}: feats[{i}] must be [F, C, H, W], got {m.dim()} dimensions")
-        if not m.is_contiguous():
-            raise RuntimeError(f"{_DEC}: feats[{i}] must be contiguous (a map is not copied silently)")
-        if m.device != scores.device:
-            raise RuntimeError(f"{_DEC}: feats[{i}] is on {m.device}, the peaks on {scores.device}")
-        r = maps[0]
-        if m.dtype not in _DTYPES or m.dtype == torch.float64:
-            raise RuntimeError(f"{_DEC}: feats must be float32, float16 or bfloat16, got {m.dtype}")
-        if m.dtype != r.dtype:
-            raise RuntimeError(f"{_DEC}: feats[{i}] has dtype {m.dtype}, feats[0] {r.dtype}")
-        if (m.shape[0], m.shape[2], m.shape[3]) != (scores.shape[0], r.shape[2], r.shape[3]):
-            raise RuntimeError(f"{_DEC}: feats[{i}] has shape {tuple(m.shape)}: F = {scores.shape[0]}, H = {r.shape[2]} and "
-                               f"W = {r.shape[3]} must agree")
-    return maps
-
-
-def _threshold(who, name, v):
-    if v is None:
-        return None
-    if math.isnan(_ops.number(who, name, v)):
-        raise RuntimeError(f"{who}: {name} must not be NaN")
-    return float(v)
-
-
-def _cut(who, name, v):
-    if v is None:
-        return None
-    if _ops.number(who, name, v, integer=True) < 1:
-        raise RuntimeError(f"{who}: {name} must be at least 1, got {v}")
-    return v
-
-
 def _detections(boxes, scores, labels, source, extras, sizes):
     return BoxDetections(*(RaggedBatch(x, sample_sizes=sizes) for x in (boxes, scores, labels, source, extras)))
-
-
-def _outputs(F, M, E, dev):
-    return (torch.empty((F, M, 4), dtype=torch.float32, device=dev), torch.empty((F, M), dtype=torch.float32, device=dev),
-            torch.empty((F, M), dtype=torch.int64, device=dev), torch.empty((F, M), dtype=torch.int32, device=dev),
-            torch.empty((F, M, E), dtype=torch.float32, device=dev))
 
 
 def box_heatmap_decode(peaks, feats, *, image_hw, image_matrices=None, score_threshold=None, scores_are_logits: bool = False,
@@ -177,8 +105,8 @@ def box_heatmap_decode(peaks, feats, *, image_hw, image_matrices=None, score_thr
     serial host entry over the same arithmetic.  All outputs of the two are bit-equal, except the score under
     ``scores_are_logits``, which depends on ``exp`` and agrees to a few ulp.  ``F == 0`` gives empty outputs without a launch.
     """
-    scores, indices, classes = _check_peaks(peaks)
-    maps = _check_feats(feats, scores)
+    scores, indices, classes = _det.check_peaks(_DEC, peaks, "F", MAX_K)
+    maps = _det.check_feats(_DEC, feats, scores, "F", MAX_MAPS)
     C = sum(m.shape[1] for m in maps)
     if not 4 <= C <= 4 + MAX_EXTRAS:
         raise RuntimeError(f"{_DEC}: the maps must hold 4..{4 + MAX_EXTRAS} channels in total (off_x, off_y, h, w and up to "
@@ -194,8 +122,8 @@ def box_heatmap_decode(peaks, feats, *, image_hw, image_matrices=None, score_thr
     if image_matrices is not None and (image_matrices.dtype != torch.float32 or tuple(image_matrices.shape) != (F, 2, 3)):
         raise RuntimeError(f"{_DEC}: image_matrices must be float32 [{F}, 2, 3], got {image_matrices.dtype} "
                            f"{tuple(image_matrices.shape)}")
-    thr = _threshold(_DEC, "score_threshold", score_threshold)
-    iou = _threshold(_DEC, "iou_threshold", iou_threshold)
+    thr = _det.threshold(_DEC, "score_threshold", score_threshold)
+    iou = _det.threshold(_DEC, "iou_threshold", iou_threshold)
     if min_size is None or _ops.is_number(min_size):
         size = None if min_size is None else (min_size, min_size)
     elif isinstance(min_size, (list, tuple)) and len(min_size) == 2 and all(_ops.is_number(v) for v in min_size):
@@ -204,15 +132,13 @@ def box_heatmap_decode(peaks, feats, *, image_hw, image_matrices=None, score_thr
         raise RuntimeError(f"{_DEC}: min_size must be a Python number, an (h, w) pair of them or None, got {min_size!r}")
     if size is not None and any(math.isnan(v) for v in size):
         raise RuntimeError(f"{_DEC}: min_size must not hold NaN, got {min_size!r}")
-    post = _cut(_DEC, "post_max_size", post_max_size)
+    post = _det.cut(_DEC, "post_max_size", post_max_size)
 
     M = K if post is None else min(K, post)
     E = C - 4
-    boxes, out_scores, labels, source, extras = _outputs(F, M, E, dev)
-    if F == 0:
-        kept = torch.zeros((F,), dtype=torch.int64, device=dev)
-    else:
-        kept = torch.empty((F,), dtype=torch.int64, device=dev)
+    boxes, out_scores, labels, source, extras = _det.empty_outputs((F, M), 4, dev, E)
+    kept = _det.kept_sizes((F,), dev)
+    if F:
         p = _nat.BoxDecodeParams()
         p.scores, p.indices, p.classes = scores.data_ptr(), indices.data_ptr(), classes.data_ptr()
         p.num_maps = len(maps)
@@ -235,19 +161,6 @@ def box_heatmap_decode(peaks, feats, *, image_hw, image_matrices=None, score_thr
     return _detections(boxes, out_scores, labels, source, extras, kept)
 
 
-def _check_tensor(name, x, dtype, rank, what):
-    if not isinstance(x, torch.Tensor):
-        raise RuntimeError(f"{_NMS}: {name} must hold a tensor")
-    if x.dim() != rank:
-        raise RuntimeError(f"{_NMS}: {name} must be {what}, got {tuple(x.shape)}")
-    if x.dtype != dtype:
-        raise RuntimeError(f"{_NMS}: {name} must be {str(dtype).replace('torch.', '')}, got {x.dtype}")
-    _ops.check_backend(_NMS, name, x.device)
-    if not x.is_contiguous():
-        raise RuntimeError(f"{_NMS}: {name} must be contiguous (it is not copied silently)")
-    return x
-
-
 def _check_detections(det):
     """boxes, scores, labels, source, extras and the shared sample sizes after every check"""
     if not isinstance(det, (list, tuple)) or len(det) != 5:
@@ -259,7 +172,7 @@ def _check_detections(det):
     for name, x, dtype, what in zip(names, det, dtypes, whats):
         if not _ops.is_ragged(x):
             raise RuntimeError(f"{_NMS}: detections.{name} must be a RaggedBatch")
-        tensors.append(_check_tensor(f"detections.{name}", x.tensor, dtype, what.count(",") + 1, what))
+        tensors.append(_det.check_tensor(_NMS, f"detections.{name}", x.tensor, dtype, what.count(",") + 1, what))
     boxes, extras = tensors[0], tensors[4]
     F, N = boxes.shape[0], boxes.shape[1]
     if boxes.shape[2] != 4:
@@ -272,19 +185,7 @@ def _check_detections(det):
         if tuple(x.shape[:2]) != (F, N) or x.device != boxes.device:
             raise RuntimeError(f"{_NMS}: detections.{name} must be {(F, N) + tuple(x.shape[2:])} on {boxes.device}, got "
                                f"{tuple(x.shape)} on {x.device}")
-    sizes = det[0].sample_sizes
-    if (not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or tuple(sizes.shape) != (F,)
-            or sizes.device != boxes.device):
-        raise RuntimeError(f"{_NMS}: the sample_sizes of detections.boxes must be an int64 tensor ({F},) on {boxes.device}")
-    if not sizes.is_contiguous():
-        raise RuntimeError(f"{_NMS}: the sample_sizes of detections.boxes must be contiguous")
-    for name, x in zip(names[1:], det[1:]):
-        other = x.sample_sizes
-        if other is not sizes and not (isinstance(other, torch.Tensor) and other.data_ptr() == sizes.data_ptr()
-                                       and other.dtype == sizes.dtype and other.shape == sizes.shape):
-            raise RuntimeError(f"{_NMS}: detections.{name} does not share the sample_sizes of detections.boxes (the five "
-                               f"members share one tensor)")
-    return (*tensors, sizes)
+    return (*tensors, _det.shared_sample_sizes(_NMS, "detections", names, det, F, boxes.device, "the five members share one tensor"))
 
 
 def nms_boxes(detections, iou_threshold, *, class_agnostic: bool = False, pre_max_size=None, post_max_size=None) -> BoxDetections:
@@ -326,16 +227,14 @@ def nms_boxes(detections, iou_threshold, *, class_agnostic: bool = False, pre_ma
     if hasattr(detections, "_asdict"):
         detections = tuple(detections)
     bx, sc, lb, src, ex, sizes = _check_detections(detections)
-    thr = _threshold(_NMS, "iou_threshold", iou_threshold)
-    pre, post = _cut(_NMS, "pre_max_size", pre_max_size), _cut(_NMS, "post_max_size", post_max_size)
+    thr = _det.threshold(_NMS, "iou_threshold", iou_threshold)
+    pre, post = _det.cut(_NMS, "pre_max_size", pre_max_size), _det.cut(_NMS, "post_max_size", post_max_size)
     F, N, E = bx.shape[0], bx.shape[1], ex.shape[2]
     dev = bx.device
     M = min(v for v in (N, pre, post) if v is not None)
-    boxes, scores, labels, source, extras = _outputs(F, M, E, dev)
-    if F == 0:
-        kept = torch.zeros((F,), dtype=torch.int64, device=dev)
-    else:
-        kept = torch.empty((F,), dtype=torch.int64, device=dev)
+    boxes, scores, labels, source, extras = _det.empty_outputs((F, M), 4, dev, E)
+    kept = _det.kept_sizes((F,), dev)
+    if F:
         p = _nat.BoxNmsParams()
         p.boxes, p.scores, p.labels, p.source, p.sizes = (x.data_ptr() for x in (bx, sc, lb, src, sizes))
         p.extras = ex.data_ptr() if E else None

@@ -19,6 +19,7 @@ import torch
 from .. import _amd_native as _nat
 from .._amd_native import operands as _ops
 from ..batching_helpers import RaggedBatch
+from . import _detections as _det
 
 MAX_TASKS = _nat.CD_MAX_TASKS
 MAX_MAPS = _nat.CD_MAX_MAPS
@@ -58,62 +59,6 @@ def _class_lists(tasks):
             ids.append(c)
         first.append(len(ids))
     return len(tasks), first, ids
-
-
-def _check_peaks(t, p, ref):
-    """scores, indices, classes of task t after every check; `ref` is task 0's scores"""
-    if not all(hasattr(p, n) for n in ("scores", "indices", "classes")):
-        raise RuntimeError(f"{_WHO}: peaks[{t}] must be a HeatmapPeaks (scores, indices, classes)")
-    s, i, c = p.scores, p.indices, p.classes
-    for name, x in (("scores", s), ("indices", i), ("classes", c)):
-        if not isinstance(x, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: peaks[{t}].{name} must be a tensor")
-        if x.dim() != 2:
-            raise RuntimeError(f"{_WHO}: peaks[{t}].{name} must be [B, K] (heatmap_peaks with per_class=False), got "
-                               f"{tuple(x.shape)}")
-        if not x.is_contiguous():
-            raise RuntimeError(f"{_WHO}: peaks[{t}].{name} must be contiguous (it is not copied silently)")
-    ref = s if ref is None else ref
-    _ops.check_backend(_WHO, "peaks", s.device)
-    if s.dtype not in _DTYPES or s.dtype == torch.float64:
-        raise RuntimeError(f"{_WHO}: peaks[{t}].scores must be float32, float16 or bfloat16, got {s.dtype}")
-    if not 1 <= s.shape[1] <= MAX_K:
-        raise RuntimeError(f"{_WHO}: K must be in 1..{MAX_K}, got {s.shape[1]}")
-    if s.dtype != ref.dtype or s.shape != ref.shape or s.device != ref.device:
-        raise RuntimeError(f"{_WHO}: peaks[{t}].scores is {s.dtype} {tuple(s.shape)} on {s.device}, peaks[0].scores "
-                           f"{ref.dtype} {tuple(ref.shape)} on {ref.device}: all tasks share B, K, dtype and device")
-    for name, x in (("indices", i), ("classes", c)):
-        if x.dtype != torch.int64 or x.shape != ref.shape or x.device != ref.device:
-            raise RuntimeError(f"{_WHO}: peaks[{t}].{name} must be int64 {tuple(ref.shape)} on {ref.device}, got {x.dtype} "
-                               f"{tuple(x.shape)} on {x.device}")
-    return s, i, c
-
-
-def _check_feats(t, feats, ref, scores):
-    """the maps of task t as a tuple after every check; `ref` is task 0's first map"""
-    maps = (feats,) if isinstance(feats, torch.Tensor) else tuple(feats) if isinstance(feats, (list, tuple)) else None
-    if not maps:
-        raise RuntimeError(f"{_WHO}: feats[{t}] must be a tensor or a non-empty sequence of tensors")
-    if len(maps) > MAX_MAPS:
-        raise RuntimeError(f"{_WHO}: at most {MAX_MAPS} maps per task are supported, feats[{t}] has {len(maps)}")
-    for i, m in enumerate(maps):
-        if not isinstance(m, torch.Tensor):
-            raise RuntimeError(f"{_WHO}: feats[{t}][{i}] must be a tensor")
-        if m.dim() != 4:
-            raise RuntimeError(f"{_WHO}: feats[{t}][{i}] must be [B, C, H, W], got {m.dim()} dimensions")
-        if not m.is_contiguous():
-            raise RuntimeError(f"{_WHO}: feats[{t}][{i}] must be contiguous (a map is not copied silently)")
-        if m.device != scores.device:
-            raise RuntimeError(f"{_WHO}: feats[{t}][{i}] is on {m.device}, the peaks on {scores.device}")
-        r = maps[0] if ref is None else ref
-        if m.dtype not in _DTYPES or m.dtype == torch.float64:
-            raise RuntimeError(f"{_WHO}: feats must be float32, float16 or bfloat16, got {m.dtype}")
-        if m.dtype != r.dtype:
-            raise RuntimeError(f"{_WHO}: feats[{t}][{i}] has dtype {m.dtype}, feats[0][0] {r.dtype}")
-        if (m.shape[0], m.shape[2], m.shape[3]) != (scores.shape[0], r.shape[2], r.shape[3]):
-            raise RuntimeError(f"{_WHO}: feats[{t}][{i}] has shape {tuple(m.shape)}: B = {scores.shape[0]}, H = {r.shape[2]} "
-                               f"and W = {r.shape[3]} must agree")
-    return maps
 
 
 def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_range, voxel_size, out_size_factor,
@@ -181,8 +126,8 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
         raise RuntimeError(f"{_WHO}: feats must hold one entry per task ({T})")
     per_task, all_maps = [], []
     for t in range(T):
-        per_task.append(_check_peaks(t, peaks[t], per_task[0][0] if per_task else None))
-        all_maps.append(_check_feats(t, feats[t], all_maps[0][0] if all_maps else None, per_task[0][0]))
+        per_task.append(_det.check_peaks(_WHO, peaks[t], "B", MAX_K, t, per_task[0][0] if per_task else None))
+        all_maps.append(_det.check_feats(_WHO, feats[t], per_task[0][0], "B", MAX_MAPS, t, all_maps[0][0] if all_maps else None))
     scores0, map0 = per_task[0][0], all_maps[0][0]
     C = sum(m.shape[1] for m in all_maps[0])
     for t, maps in enumerate(all_maps):
@@ -201,8 +146,7 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
                            f"{out_size_factor!r}")
     if not (math.isfinite(pc[0]) and math.isfinite(pc[1])):
         raise RuntimeError(f"{_WHO}: pc_range must be finite, got {pc_range!r}")
-    if score_threshold is not None and math.isnan(_ops.number(_WHO, "score_threshold", score_threshold)):
-        raise RuntimeError(f"{_WHO}: score_threshold must not be NaN")
+    thr = _det.threshold(_WHO, "score_threshold", score_threshold)
     rng = None if post_center_range is None else _numbers("post_center_range", post_center_range, 6, exact=True)
     if rng is not None and any(math.isnan(v) for v in rng):
         raise RuntimeError(f"{_WHO}: post_center_range must not hold NaN, got {post_center_range!r}")
@@ -213,33 +157,24 @@ def center_point_decode(peaks, feats, tasks: Sequence[Sequence[int]], *, pc_rang
     else:
         raise RuntimeError(f"{_WHO}: nms_threshold must be a number, a sequence of {T} numbers (one per task) or None, got "
                            f"{nms_threshold!r}")
-    for t, v in enumerate(nms):
-        if v is not None and math.isnan(_ops.number(_WHO, f"nms_threshold[{t}]", v)):
-            raise RuntimeError(f"{_WHO}: nms_threshold[{t}] must not be NaN")
-    if post_max_size is not None and _ops.number(_WHO, "post_max_size", post_max_size, integer=True) < 1:
-        raise RuntimeError(f"{_WHO}: post_max_size must be at least 1, got {post_max_size}")
+    nms = [_det.threshold(_WHO, f"nms_threshold[{t}]", v) for t, v in enumerate(nms)]
+    post_max_size = _det.cut(_WHO, "post_max_size", post_max_size)
 
     dev = scores0.device
     M = K if post_max_size is None else min(K, post_max_size)
-    shape = (T, B, M)
-    boxes = torch.empty(shape + (C - 1,), dtype=torch.float32, device=dev)
-    out_scores = torch.empty(shape, dtype=torch.float32, device=dev)
-    labels = torch.empty(shape, dtype=torch.int64, device=dev)
-    source = torch.empty(shape, dtype=torch.int32, device=dev)
-    if B == 0:
-        kept = torch.zeros((T, B), dtype=torch.int64, device=dev)
-    else:
-        kept = torch.empty((T, B), dtype=torch.int64, device=dev)
+    boxes, out_scores, labels, source = _det.empty_outputs((T, B, M), C - 1, dev)
+    kept = _det.kept_sizes((T, B), dev)
+    if B:
         p = _nat.CenterPointDecodeParams()
         for t, ((s, i, c), maps) in enumerate(zip(per_task, all_maps)):
             p.scores[t], p.indices[t], p.classes[t] = s.data_ptr(), i.data_ptr(), c.data_ptr()
             p.num_maps[t] = len(maps)
             for n, m in enumerate(maps):
                 p.maps[t][n], p.channels[t][n] = m.data_ptr(), m.shape[1]
-            p.has_nms[t], p.nms_threshold[t] = (0, 0.0) if nms[t] is None else (1, float(nms[t]))
+            p.has_nms[t], p.nms_threshold[t] = (0, 0.0) if nms[t] is None else (1, nms[t])
         p.pc_range[0], p.pc_range[1], p.voxel_size[0], p.voxel_size[1] = pc[0], pc[1], vs[0], vs[1]
         p.out_size_factor = float(factor)
-        p.has_score_threshold, p.score_threshold = (0, 0.0) if score_threshold is None else (1, float(score_threshold))
+        p.has_score_threshold, p.score_threshold = (0, 0.0) if thr is None else (1, thr)
         p.has_post_center_range = 0 if rng is None else 1
         for n, v in enumerate(rng or ()):
             p.post_center_range[n] = v

@@ -27,6 +27,7 @@ from torch.autograd.function import once_differentiable
 from .. import _amd_native as _nat
 from .._amd_native import operands as _ops
 from ..batching_helpers import RaggedBatch
+from . import _detections as _det
 
 _DTYPES = _nat.FLOAT_DTYPE_CODES
 _KINDS = {"l1": _nat.CR_L1, "smooth_l1": _nat.CR_SMOOTH_L1}
@@ -36,9 +37,7 @@ MAX_CHANNELS = _nat.CR_MAX_CHANNELS
 
 def _check_feats(who, feats):
     """the maps as a tuple, after every check that needs no device"""
-    maps = (feats,) if isinstance(feats, torch.Tensor) else tuple(feats) if isinstance(feats, (list, tuple)) else None
-    if maps is None or not maps:
-        raise RuntimeError(f"{who}: feats must be a tensor or a non-empty sequence of tensors")
+    maps = _det.maps_of(who, "feats", feats)
     if len(maps) > MAX_MAPS:
         raise RuntimeError(f"{who}: at most {MAX_MAPS} maps are supported, got {len(maps)}")
     for i, m in enumerate(maps):

@@ -23,6 +23,7 @@ import torch
 from .. import _amd_native as _nat
 from .._amd_native import operands as _ops
 from ..batching_helpers import RaggedBatch
+from . import _detections as _det
 from .box_decode import BoxDetections
 from .center_decode import CenterPointDetections
 
@@ -56,23 +57,6 @@ def _check_head(who, cls_scores, bbox_preds, max_num, widths):
     if max_num > Q * C:
         raise RuntimeError(f"{who}: max_num = {max_num} exceeds Q * C = {Q * C}")
     return B, Q, C, D
-
-
-def _threshold(who, v):
-    if v is None:
-        return None
-    if math.isnan(_ops.number(who, "score_threshold", v)):
-        raise RuntimeError(f"{who}: score_threshold must not be NaN")
-    return float(v)
-
-
-def _outputs(B, M, W, dev):
-    return (torch.empty((B, M, W), dtype=torch.float32, device=dev), torch.empty((B, M), dtype=torch.float32, device=dev),
-            torch.empty((B, M), dtype=torch.int64, device=dev), torch.empty((B, M), dtype=torch.int32, device=dev))
-
-
-def _sizes(B, dev):
-    return torch.zeros((B,), dtype=torch.int64, device=dev) if B == 0 else torch.empty((B,), dtype=torch.int64, device=dev)
 
 
 def query_box_decode_3d(cls_scores, bbox_preds, max_num, *, score_threshold=None, post_center_range=None,
@@ -124,7 +108,7 @@ def query_box_decode_3d(cls_scores, bbox_preds, max_num, *, score_threshold=None
     Out of scope: softmax-with-background heads, a ``D`` other than 8 or 10, regression outputs wider than ``D``.
     """
     B, Q, C, D = _check_head(_D3, cls_scores, bbox_preds, max_num, (8, 10))
-    thr = _threshold(_D3, score_threshold)
+    thr = _det.threshold(_D3, "score_threshold", score_threshold)
     rng = None
     if post_center_range is not None:
         if not isinstance(post_center_range, (list, tuple)) or len(post_center_range) != 6:
@@ -134,8 +118,8 @@ def query_box_decode_3d(cls_scores, bbox_preds, max_num, *, score_threshold=None
             raise RuntimeError(f"{_D3}: post_center_range must not hold NaN, got {post_center_range!r}")
     dev = cls_scores.device
     M = max_num
-    boxes, scores, labels, source = _outputs(B, M, D - 1, dev)
-    kept = _sizes(B, dev)
+    boxes, scores, labels, source = _det.empty_outputs((B, M), D - 1, dev)
+    kept = _det.kept_sizes((B,), dev)
     if B:
         p = _nat.QueryDecode3dParams()
         p.cls_scores, p.bbox_preds = cls_scores.data_ptr(), bbox_preds.data_ptr()
@@ -198,12 +182,11 @@ def query_box_decode_2d(cls_scores, bbox_preds, max_num, *, image_hw, image_matr
     if image_matrices is not None and (image_matrices.dtype != torch.float32 or tuple(image_matrices.shape) != (B, 2, 3)):
         raise RuntimeError(f"{_D2}: image_matrices must be float32 [{B}, 2, 3], got {image_matrices.dtype} "
                            f"{tuple(image_matrices.shape)}")
-    thr = _threshold(_D2, score_threshold)
+    thr = _det.threshold(_D2, "score_threshold", score_threshold)
     dev = cls_scores.device
     M = max_num
-    boxes, scores, labels, source = _outputs(B, M, 4, dev)
-    extras = torch.empty((B, M, 0), dtype=torch.float32, device=dev)
-    kept = _sizes(B, dev)
+    boxes, scores, labels, source, extras = _det.empty_outputs((B, M), 4, dev, 0)
+    kept = _det.kept_sizes((B,), dev)
     if B:
         p = _nat.QueryDecode2dParams()
         p.cls_scores, p.bbox_preds = cls_scores.data_ptr(), bbox_preds.data_ptr()

@@ -15,6 +15,7 @@ import torch
 from .. import _amd_native as _nat
 from .._amd_native import operands as _ops
 from ..batching_helpers import RaggedBatch
+from . import _detections as _det
 from .center_decode import CenterPointDetections
 
 MAX_TASKS = _nat.RN_MAX_TASKS
@@ -23,29 +24,6 @@ MIN_D = _nat.RN_MIN_D
 MAX_D = _nat.RN_MAX_D
 _IOU = "rotated_iou_bev"
 _NMS = "rotated_nms_bev"
-
-
-def _sizes_of(who, name, ragged, B, device):
-    sizes = ragged.sample_sizes
-    if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or tuple(sizes.shape) != (B,) or sizes.device != device:
-        raise RuntimeError(f"{who}: the sample_sizes of {name} must be an int64 tensor ({B},) on {device}")
-    if not sizes.is_contiguous():
-        raise RuntimeError(f"{who}: the sample_sizes of {name} must be contiguous")
-    return sizes
-
-
-def _check_tensor(who, name, x, dtype, rank, what):
-    if not isinstance(x, torch.Tensor):
-        raise RuntimeError(f"{who}: {name} must hold a tensor")
-    if x.dim() != rank:
-        raise RuntimeError(f"{who}: {name} must be {what}, got {tuple(x.shape)}")
-    if x.dtype != dtype:
-        raise RuntimeError(f"{who}: {name} must be {str(dtype).replace('torch.', '')}, got {x.dtype}")
-    if x.device.type not in ("cuda", "cpu"):
-        raise RuntimeError(f"{who}: {name} must be a CUDA or CPU tensor, got {x.device}")
-    if not x.is_contiguous():
-        raise RuntimeError(f"{who}: {name} must be contiguous (it is not copied silently)")
-    return x
 
 
 def rotated_iou_bev(boxes_a, boxes_b):
@@ -77,7 +55,7 @@ def rotated_iou_bev(boxes_a, boxes_b):
     metres apart along their length.  Nothing takes a gradient.  GPU tensors run one HIP kernel on
     torch's current stream, CPU tensors the library's serial host entry over the same arithmetic.
     """
-    ta, tb = [_check_tensor(_IOU, name, getattr(x, "tensor", None), torch.float32, 3, "[B, N, 5]")
+    ta, tb = [_det.check_tensor(_IOU, name, getattr(x, "tensor", None), torch.float32, 3, "[B, N, 5]", each=True)
               for name, x in (("boxes_a", boxes_a), ("boxes_b", boxes_b))]
     if ta.shape[2] != 5 or tb.shape[2] != 5:
         raise RuntimeError(f"{_IOU}: the boxes must be [B, N, 5] as (x, y, dx, dy, yaw), got {tuple(ta.shape)} and {tuple(tb.shape)}")
@@ -87,22 +65,12 @@ def rotated_iou_bev(boxes_a, boxes_b):
         raise RuntimeError(f"{_IOU}: boxes_a is on {ta.device}, boxes_b on {tb.device}")
     B, Na, Nb = ta.shape[0], ta.shape[1], tb.shape[1]
     dev = ta.device
-    sa, sb = _sizes_of(_IOU, "boxes_a", boxes_a, B, dev), _sizes_of(_IOU, "boxes_b", boxes_b, B, dev)
+    sa, sb = _det.sizes_of(_IOU, "boxes_a", boxes_a, B, dev), _det.sizes_of(_IOU, "boxes_b", boxes_b, B, dev)
     out = torch.empty((B, Na, Nb), dtype=torch.float32, device=dev)
     if out.numel():
         args = (ta.data_ptr(), sa.data_ptr(), tb.data_ptr(), sb.data_ptr(), B, Na, Nb, out.data_ptr())
         _ops.run("accv_rotated_iou_bev", args, dev, _IOU)
     return RaggedBatch(out, sample_sizes=sa)
-
-
-def _cut(name, v):
-    if v is None:
-        return None
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise RuntimeError(f"{_NMS}: {name} must be a Python integer or None, got {v!r}")
-    if v < 1:
-        raise RuntimeError(f"{_NMS}: {name} must be at least 1, got {v}")
-    return v
 
 
 def _check_task(t, det, ref):
@@ -116,7 +84,8 @@ def _check_task(t, det, ref):
         if not _ops.is_ragged(x):
             raise RuntimeError(f"{_NMS}: detections[{t}].{name} must be a RaggedBatch")
         rank = 3 if name == "boxes" else 2
-        tensors.append(_check_tensor(_NMS, f"detections[{t}].{name}", x.tensor, dtype, rank, "[B, N, D]" if rank == 3 else "[B, N]"))
+        tensors.append(_det.check_tensor(_NMS, f"detections[{t}].{name}", x.tensor, dtype, rank, "[B, N, D]" if rank == 3 else "[B, N]",
+                                         each=True))
     boxes = tensors[0]
     ref = boxes if ref is None else ref
     B, N, D = boxes.shape
@@ -130,14 +99,8 @@ def _check_task(t, det, ref):
     for name, x in zip(names[1:], tensors[1:]):
         if tuple(x.shape) != (B, N) or x.device != boxes.device:
             raise RuntimeError(f"{_NMS}: detections[{t}].{name} must be {(B, N)} on {boxes.device}, got {tuple(x.shape)} on {x.device}")
-    sizes = _sizes_of(_NMS, f"detections[{t}].boxes", det[0], B, boxes.device)
-    for name, x in zip(names[1:], det[1:]):
-        other = x.sample_sizes
-        if other is not sizes and not (isinstance(other, torch.Tensor) and other.data_ptr() == sizes.data_ptr()
-                                       and other.dtype == sizes.dtype and other.shape == sizes.shape):
-            raise RuntimeError(f"{_NMS}: detections[{t}].{name} does not share the sample_sizes of detections[{t}].boxes "
-                               f"(the four members of a task share one tensor)")
-    return (*tensors, sizes)
+    return (*tensors, _det.shared_sample_sizes(_NMS, f"detections[{t}]", names, det, B, boxes.device,
+                                               "the four members of a task share one tensor"))
 
 
 def rotated_nms_bev(detections, iou_threshold, *, pre_max_size=None, post_max_size=None) -> List[CenterPointDetections]:
@@ -204,21 +167,15 @@ def rotated_nms_bev(detections, iou_threshold, *, pre_max_size=None, post_max_si
             raise RuntimeError(f"{_NMS}: iou_threshold[{t}] must be a Python number or None, got {v!r}")
         if math.isnan(v):
             raise RuntimeError(f"{_NMS}: iou_threshold[{t}] must not be NaN")
-    pre, post = _cut("pre_max_size", pre_max_size), _cut("post_max_size", post_max_size)
+    pre, post = _det.cut(_NMS, "pre_max_size", pre_max_size, " or None"), _det.cut(_NMS, "post_max_size", post_max_size, " or None")
 
     boxes0 = per_task[0][0]
     B, N, D = boxes0.shape
     dev = boxes0.device
     M = min(v for v in (N, pre, post) if v is not None)
-    shape = (T, B, M)
-    boxes = torch.empty(shape + (D,), dtype=torch.float32, device=dev)
-    scores = torch.empty(shape, dtype=torch.float32, device=dev)
-    labels = torch.empty(shape, dtype=torch.int64, device=dev)
-    source = torch.empty(shape, dtype=torch.int32, device=dev)
-    if B == 0:
-        kept = torch.zeros((T, B), dtype=torch.int64, device=dev)
-    else:
-        kept = torch.empty((T, B), dtype=torch.int64, device=dev)
+    boxes, scores, labels, source = _det.empty_outputs((T, B, M), D, dev)
+    kept = _det.kept_sizes((T, B), dev)
+    if B:
         p = _nat.RotatedNmsParams()
         for t, (bx, sc, lb, src, sizes) in enumerate(per_task):
             p.boxes[t], p.scores[t], p.labels[t], p.source[t], p.sizes[t] = (x.data_ptr() for x in (bx, sc, lb, src, sizes))

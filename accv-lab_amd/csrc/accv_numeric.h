@@ -123,6 +123,15 @@ __host__ __device__ inline typename Compute<DT>::type load(const void* p, long l
     else return bf16_bits_to_float(static_cast<const uint16_t*>(p)[off]);
 }
 
+// element `off` of a tensor of dtype code dt (f32, f16 or bf16), widened exactly (the software f16 conversion: the same on
+// host and device)
+__host__ __device__ inline float load_any(const void* p, long long off, int dt)
+{
+    if (dt == kF32) return load<kF32>(p, off);
+    if (dt == kF16) return load<kF16>(p, off);
+    return load<kBF16>(p, off);
+}
+
 // v narrowed to dtype DT at element `off`
 template <int DT, bool HW = false>
 __host__ __device__ inline void store(void* p, long long off, typename Compute<DT>::type v)

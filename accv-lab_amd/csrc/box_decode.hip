@@ -32,6 +32,7 @@
 #include "accv_common.h"
 #include "accv_numeric.h"
 #include "box_decode_arith.h"
+#include "detect_common.h"
 
 #pragma clang fp contract(off)
 
@@ -39,15 +40,16 @@ namespace {
 
 using namespace accv_bd;
 
+using accv::load_any;
+using accv_det::clamp_size;
+
 constexpr int kWave = 64;
 constexpr int kThreads = 256;               // and slots per chunk
-constexpr int kWaves = kThreads / kWave;
-constexpr int kChunks = kMaxK / kThreads;   // chunks a workgroup walks at most
-constexpr int kBlocks = kMaxK / kWave;      // NMS blocks at most
+using Geo = accv_det::Geometry<kMaxK, kThreads, kWave>;
+constexpr int kWaves = Geo::kWaves, kChunks = Geo::kChunks, kBlocks = Geo::kBlocks;
 
 static_assert(kMaxMaps == ACCV_BD_MAX_MAPS && kMaxExtras == ACCV_BD_MAX_EXTRAS && kMaxK == ACCV_BD_MAX_K,
               "box_decode_arith.h and accv_hip.h disagree");
-static_assert(kMaxK % kThreads == 0 && kChunks <= 32, "a lane keeps one alive bit per chunk");
 
 // the prepared boxes of a workgroup, structure of arrays
 struct Staged {
@@ -68,8 +70,6 @@ struct Staged {
         return b;
     }
 };
-
-__host__ __device__ inline long long clamp_size(long long v, long long hi) { return v < 0 ? 0 : v > hi ? hi : v; }
 
 // ======================================================================================================= shared phases
 // Phase 2.  n: slots of the frame (every chunk below ceil(n / kThreads) is staged in full); alive: bit c = my slot of chunk
@@ -112,19 +112,6 @@ __device__ inline void greedy_walk(const Staged& sb, unsigned long long* s_keep,
     }
 }
 
-// Phase 3, first half: the number of kept boxes, and for my wave's block of chunk c the output slot of its lane 0
-__device__ inline int slot_bases(const unsigned long long* s_keep, int (&base)[kChunks])
-{
-    const int wave = threadIdx.x / kWave;
-    int total = 0;
-#pragma unroll
-    for (int j = 0; j < kBlocks; ++j) {
-        if (j % kWaves == wave) base[j / kWaves] = total;
-        total += __popcll(s_keep[j]);
-    }
-    return total;
-}
-
 // ============================================================================================================== decode
 struct DecodeArgs {
     const void* scores;                  // [F, K]
@@ -144,14 +131,6 @@ struct DecodeArgs {
     long long F, K, M, Wm, Hm, plane, Wi, Hi;
     int E, score_dt, map_dt, hw64;
 };
-
-// element `off` of a tensor of dtype code dt, widened exactly (the software f16 conversion: the same on host and device)
-__host__ __device__ inline float load_any(const void* p, long long off, int dt)
-{
-    if (dt == accv::kF32) return accv::load<accv::kF32>(p, off);
-    if (dt == accv::kF16) return accv::load<accv::kF16>(p, off);
-    return accv::load<accv::kBF16>(p, off);
-}
 
 // concatenated channel c at `cell` of frame f
 __host__ __device__ inline float channel_at(const DecodeArgs& a, int c, long long f, long long cell)
@@ -263,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void box_decode_kernel(const DecodeArgs a
 
     // 3. output slots from the kept masks, rows, padding, count
     int base[kChunks];
-    const int total = slot_bases(s_keep, base);
+    const int total = Geo::slot_bases(s_keep, base);
     const accv_ip::Warp w = warp_of(a.matrices, f);
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {   // unrolled: base[] stays in registers
@@ -335,13 +314,7 @@ int decode_check_args(const char* who, const accv_box_decode_params* p, long lon
         return ACCV_OK;
     }
     const int E = (int)C - 4;
-    if (!boxes || !out_scores || !labels || !source || !out_sizes || (E > 0 && !extras)) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
-    if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_scores) | reinterpret_cast<uintptr_t>(source) |
-         (E > 0 ? reinterpret_cast<uintptr_t>(extras) : 0)) & 3u)
-        return accv::fail(ACCV_EINVAL, "%s: a 4-byte output is not aligned to its element size", who);
-    if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(out_sizes)) & 7u)
-        return accv::fail(ACCV_EINVAL, "%s: labels and sizes must be 8-byte aligned", who);
-    if (F > accv::kGridLimit) return accv::fail(ACCV_EINVAL, "%s: %lld workgroups exceed the grid limit", who, F);
+    if (int rc = accv_det::check_outputs(who, F, boxes, out_scores, labels, source, out_sizes, E > 0, extras)) return rc;
     const long long plane = Hm * Wm;
     if (F > LLONG_MAX / 64 / kMaxChannels / plane || F > LLONG_MAX / 64 / kMaxChannels / K) return accv::fail(ACCV_EINVAL, "%s: sizes overflow", who);
     const uintptr_t score_mask = (uintptr_t)accv::elem_size(p->score_dtype) - 1u, map_size = (uintptr_t)accv::elem_size(p->map_dtype);
@@ -352,17 +325,7 @@ int decode_check_args(const char* who, const accv_box_decode_params* p, long lon
     if (reinterpret_cast<uintptr_t>(p->image_hw) & (p->image_hw_i64 ? 7u : 3u))
         return accv::fail(ACCV_EINVAL, "%s: image_hw is not aligned to its element size", who);
     if (reinterpret_cast<uintptr_t>(p->image_matrices) & 3u) return accv::fail(ACCV_EINVAL, "%s: image_matrices is not aligned to its element size", who);
-    int c = 0;
-    for (int i = 0; i < p->num_maps; ++i) {
-        if (p->channels[i] == 0) continue;
-        if (!p->maps[i]) return accv::fail(ACCV_EINVAL, "%s: map %d is null", who, i);
-        if (reinterpret_cast<uintptr_t>(p->maps[i]) & (map_size - 1u)) return accv::fail(ACCV_EINVAL, "%s: map %d is not aligned to its element size", who, i);
-        for (int local = 0; local < p->channels[i]; ++local, ++c) {
-            a.chan[c] = static_cast<const char*>(p->maps[i]) + (size_t)local * (size_t)plane * map_size;
-            a.chan_count[c] = (unsigned char)p->channels[i];
-        }
-    }
-    for (; c < kMaxChannels; ++c) a.chan[c] = nullptr, a.chan_count[c] = 0;
+    if (int rc = accv_det::fill_planes(who, "", p->maps, p->channels, p->num_maps, plane, map_size, kMaxChannels, a.chan, a.chan_count)) return rc;
     a.scores = p->scores, a.indices = p->indices, a.classes = p->classes;
     a.image_hw = p->image_hw, a.matrices = p->image_matrices;
     a.boxes = boxes, a.out_scores = out_scores, a.labels = labels, a.source = source, a.extras = extras, a.sizes = out_sizes;
@@ -455,7 +418,7 @@ __global__ __launch_bounds__(kThreads) void box_nms_kernel(const NmsArgs a)
 
     // 3. output slots from the kept masks, rows, padding, count
     int base[kChunks];
-    const int total = slot_bases(s_keep, base);
+    const int total = Geo::slot_bases(s_keep, base);
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {   // unrolled: base[] stays in registers
         const int k = c * kThreads + tid;

@@ -27,6 +27,7 @@
 #include "accv_common.h"
 #include "accv_numeric.h"
 #include "center_decode_arith.h"
+#include "detect_common.h"
 
 #pragma clang fp contract(off)
 
@@ -34,16 +35,16 @@ namespace {
 
 using namespace accv_cd;
 
+using accv::load_any;
+
 constexpr int kWave = 64;
 constexpr int kThreads = 256;               // and peaks per chunk
-constexpr int kWaves = kThreads / kWave;
-constexpr int kChunks = kMaxK / kThreads;   // chunks a workgroup walks at most
-constexpr int kBlocks = kMaxK / kWave;      // NMS blocks at most
+using Geo = accv_det::Geometry<kMaxK, kThreads, kWave>;
+constexpr int kWaves = Geo::kWaves, kChunks = Geo::kChunks, kBlocks = Geo::kBlocks;
 
 static_assert(kMaxTasks == ACCV_CD_MAX_TASKS && kMaxMaps == ACCV_CD_MAX_MAPS && kMaxClasses == ACCV_CD_MAX_CLASSES &&
                   kMaxK == ACCV_CD_MAX_K,
               "center_decode_arith.h and accv_hip.h disagree");
-static_assert(kMaxK % kThreads == 0 && kChunks <= 32, "a lane keeps one alive bit per chunk");
 
 struct Args {
     const void* scores[kMaxTasks];                  // [B, K]
@@ -64,18 +65,10 @@ struct Args {
     int C, T, score_dt, map_dt;
 };
 
-// element `off` of a tensor of dtype code dt, widened exactly (the software f16 conversion: the same on host and device)
-__host__ __device__ inline float load_any(const void* p, long long off, int dt)
-{
-    if (dt == accv::kF32) return accv::load<accv::kF32>(p, off);
-    if (dt == accv::kF16) return accv::load<accv::kF16>(p, off);
-    return accv::load<accv::kBF16>(p, off);
-}
-
 // concatenated channel c of task t at `cell` of frame b
 __host__ __device__ inline float channel_at(const Args& a, int t, int c, long long b, long long cell)
 {
-    return load_any(a.chan[t][c], b * (long long)a.chan_count[t][c] * a.plane + cell, a.map_dt);
+    return accv_det::channel_at(a.chan[t], a.chan_count[t], a.plane, a.map_dt, c, b, cell);
 }
 
 // steps 1 to 4 for peak k of (b, t): whether it is valid, and its centre, height, score, cell and global class id.  An
@@ -292,12 +285,7 @@ int check_args(const char* who, const accv_center_point_decode_params* p, long l
         *empty = 1;
         return ACCV_OK;
     }
-    if (!boxes || !out_scores || !labels || !source || !out_sizes) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
-    if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_scores) | reinterpret_cast<uintptr_t>(source)) & 3u)
-        return accv::fail(ACCV_EINVAL, "%s: a 4-byte output is not aligned to its element size", who);
-    if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(out_sizes)) & 7u)
-        return accv::fail(ACCV_EINVAL, "%s: labels and sizes must be 8-byte aligned", who);
-    if (B > accv::kGridLimit) return accv::fail(ACCV_EINVAL, "%s: %lld workgroups exceed the grid limit", who, B);
+    if (int rc = accv_det::check_outputs(who, B, boxes, out_scores, labels, source, out_sizes)) return rc;
     const long long plane = H * W;
     if (B > LLONG_MAX / 64 / kMaxChannels / plane || B > LLONG_MAX / 64 / kMaxChannels / kMaxTasks / K)
         return accv::fail(ACCV_EINVAL, "%s: sizes overflow", who);
@@ -308,18 +296,11 @@ int check_args(const char* who, const accv_center_point_decode_params* p, long l
             ((reinterpret_cast<uintptr_t>(p->indices[t]) | reinterpret_cast<uintptr_t>(p->classes[t])) & 7u))
             return accv::fail(ACCV_EINVAL, "%s: the peaks of task %d are not aligned to their element size", who, t);
         a.scores[t] = p->scores[t], a.indices[t] = p->indices[t], a.classes[t] = p->classes[t];
-        int c = 0;
-        for (int i = 0; i < p->num_maps[t]; ++i) {
-            if (p->channels[t][i] == 0) continue;
-            if (!p->maps[t][i]) return accv::fail(ACCV_EINVAL, "%s: map %d of task %d is null", who, i, t);
-            if (reinterpret_cast<uintptr_t>(p->maps[t][i]) & (map_size - 1u))
-                return accv::fail(ACCV_EINVAL, "%s: map %d of task %d is not aligned to its element size", who, i, t);
-            for (int local = 0; local < p->channels[t][i]; ++local, ++c) {
-                a.chan[t][c] = static_cast<const char*>(p->maps[t][i]) + (size_t)local * (size_t)plane * map_size;
-                a.chan_count[t][c] = (unsigned char)p->channels[t][i];
-            }
-        }
-        for (; c < kMaxChannels; ++c) a.chan[t][c] = nullptr, a.chan_count[t][c] = 0;
+        char of[32];
+        snprintf(of, sizeof of, " of task %d", t);
+        if (int rc = accv_det::fill_planes(who, of, p->maps[t], p->channels[t], p->num_maps[t], plane, map_size, kMaxChannels, a.chan[t],
+                                           a.chan_count[t]))
+            return rc;
         a.nms[t] = (float)p->nms_threshold[t];
         a.has_nms[t] = p->has_nms[t] ? 1 : 0;
     }

@@ -27,6 +27,7 @@
 
 #include "accv_common.h"
 #include "accv_numeric.h"
+#include "detect_common.h"
 #include "query_decode_arith.h"
 #include "topk_select.h"
 
@@ -34,6 +35,7 @@
 
 namespace {
 
+using accv::load_any;
 using accv_topk::u64;
 
 constexpr int kWave = 64;
@@ -45,14 +47,6 @@ constexpr int kMaxD = 10;        // values of the widest input row
 static_assert(accv_qd::kMaxK == ACCV_QD_MAX_K && accv_qd::kMaxK == kThreads && accv_qd::kMaxK <= accv_topk::kMaxK,
               "a lane per rank; query_decode_arith.h and accv_hip.h must agree");
 static_assert(accv_qd::kMaxWidth == kMaxD - 1, "the widest written row");
-
-// element `off` of a tensor of dtype code dt, widened exactly (the software f16 conversion: the same on host and device)
-__host__ __device__ inline float load_any(const void* p, long long off, int dt)
-{
-    if (dt == accv::kF32) return accv::load<accv::kF32>(p, off);
-    if (dt == accv::kF16) return accv::load<accv::kF16>(p, off);
-    return accv::load<accv::kBF16>(p, off);
-}
 
 // ======================================================================================================== row decoders
 // A row decoder: D values in, width() values out, the constants of a frame, and decode() = score, row and validity.
@@ -250,16 +244,13 @@ int check_common(const char* who, const void* cls, const void* rows, int cls_dt,
         *empty = 1;
         return ACCV_OK;
     }
-    if (!boxes || !scores || !labels || !source || !out_sizes) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
+    if (int rc = accv_det::outputs_present(who, boxes, scores, labels, source, out_sizes)) return rc;
     if (!cls || !rows) return accv::fail(ACCV_EINVAL, "%s: null input pointer", who);
-    if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(source)) & 3u)
-        return accv::fail(ACCV_EINVAL, "%s: a 4-byte output is not aligned to its element size", who);
-    if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(out_sizes)) & 7u)
-        return accv::fail(ACCV_EINVAL, "%s: labels and sizes must be 8-byte aligned", who);
+    if (int rc = accv_det::outputs_aligned(who, boxes, scores, labels, source, out_sizes)) return rc;
     if ((reinterpret_cast<uintptr_t>(cls) & ((uintptr_t)accv::elem_size(cls_dt) - 1u)) ||
         (reinterpret_cast<uintptr_t>(rows) & ((uintptr_t)accv::elem_size(row_dt) - 1u)))
         return accv::fail(ACCV_EINVAL, "%s: an input is not aligned to its element size", who);
-    if (B > accv::kGridLimit) return accv::fail(ACCV_EINVAL, "%s: %lld workgroups exceed the grid limit", who, B);
+    if (int rc = accv_det::grid_fits(who, B)) return rc;
     if (B > LLONG_MAX / 64 / kMaxD / (Q * C)) return accv::fail(ACCV_EINVAL, "%s: sizes overflow", who);
     a.cls = cls, a.rows = rows;
     a.boxes = boxes, a.scores = scores, a.labels = labels, a.source = source, a.sizes = out_sizes;

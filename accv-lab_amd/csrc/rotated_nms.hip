@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "accv_common.h"
+#include "detect_common.h"
 #include "rotated_iou_arith.h"
 
 #pragma clang fp contract(off)
@@ -37,15 +38,14 @@ using namespace accv_ri;
 
 constexpr int kMaxTasks = ACCV_RN_MAX_TASKS;
 constexpr int kMaxN = ACCV_RN_MAX_N;
+using accv_det::clamp_size;
 constexpr int kWave = 64;
 constexpr int kThreads = 256;               // and slots per chunk
-constexpr int kWaves = kThreads / kWave;
-constexpr int kChunks = kMaxN / kThreads;   // chunks a workgroup walks at most
-constexpr int kBlocks = kMaxN / kWave;      // NMS blocks at most
+using Geo = accv_det::Geometry<kMaxN, kThreads, kWave>;
+constexpr int kWaves = Geo::kWaves, kChunks = Geo::kChunks, kBlocks = Geo::kBlocks;
 constexpr int kTile = 64;                   // IoU matrix: rows and columns per workgroup
 constexpr int kCols[5] = {0, 1, 3, 4, 6};   // (x, y, dx, dy, yaw) inside a box row
 
-static_assert(kMaxN % kThreads == 0 && kChunks <= 32, "a lane keeps one alive bit per chunk");
 static_assert(kTile == kWave && kThreads % kTile == 0, "a wave covers a row of a tile");
 
 // the prepared boxes of a workgroup, structure of arrays (a lane per box: conflict-free; one box for all: broadcast)
@@ -76,8 +76,6 @@ __host__ __device__ inline Box no_box()
     b.ok = false;
     return b;
 }
-
-__host__ __device__ inline long long clamp_size(long long v, long long hi) { return v < 0 ? 0 : v > hi ? hi : v; }
 
 // ================================================================================================================ IoU
 struct IouArgs {
@@ -351,12 +349,7 @@ int nms_check_args(const char* who, const accv_rotated_nms_params* p, long long 
         *empty = 1;
         return ACCV_OK;
     }
-    if (!boxes || !scores || !labels || !source || !out_sizes) return accv::fail(ACCV_EINVAL, "%s: null output pointer", who);
-    if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(source)) & 3u)
-        return accv::fail(ACCV_EINVAL, "%s: a 4-byte output is not aligned to its element size", who);
-    if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(out_sizes)) & 7u)
-        return accv::fail(ACCV_EINVAL, "%s: labels and sizes must be 8-byte aligned", who);
-    if (B > accv::kGridLimit) return accv::fail(ACCV_EINVAL, "%s: %lld workgroups exceed the grid limit", who, B);
+    if (int rc = accv_det::check_outputs(who, B, boxes, scores, labels, source, out_sizes)) return rc;
     if (B > LLONG_MAX / 64 / kMaxTasks / ACCV_RN_MAX_D / N) return accv::fail(ACCV_EINVAL, "%s: sizes overflow", who);
     for (int t = 0; t < T; ++t) {
         if (!p->boxes[t] || !p->scores[t] || !p->labels[t] || !p->source[t] || !p->sizes[t])
