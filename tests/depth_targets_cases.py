@@ -14,6 +14,8 @@ apart and see less than that (53 degrees), so a point placed for one camera is f
 left out of the float64 comparison.  `random_case` scatters points with overlapping cameras and hostile values; it is
 compared against (a) only.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -419,6 +421,36 @@ def check_empty(dev):
     case = random_case(31, (300, 300), 2, 3, 3, (32, 48))
     want = definition(case["points"], [300, 0], case["projection"], **kw)
     check_equal(run(dict(case, sizes=np.array([10 ** 6, -5])), dev, **kw), want, "clamped sizes")
+
+
+@functools.lru_cache(maxsize=None)
+def most_frames_case():
+    """B = 65535 frames of at most two points, one camera, 2 x 2 maps: (case, kw, want), built once for both test files and
+    never written to.  Under IDENTITY d is z itself, so every frame has depths of its own"""
+    B = 65535
+    rng = np.random.default_rng(71)
+    rows = np.stack([rng.uniform(-1, 5, 2 * B), rng.uniform(-1, 5, 2 * B), rng.uniform(1, 64, 2 * B)], axis=1)
+    case = dict(points=uvd(rows).reshape(B, 2, 3), sizes=rng.integers(0, 3, B),
+                projection=np.ascontiguousarray(np.broadcast_to(IDENTITY[None, None], (B, 1, 3, 4))))
+    kw = dict(image_hw=(4, 4), downsample=2, depth_range=DEPTH_RANGE, depth_bins=BINS)
+    want = definition(case["points"], case["sizes"], case["projection"], **kw)
+    filled = (want[0] != 0).reshape(B, -1).sum(1)
+    assert sorted(np.unique(filled).tolist()) == [0, 1, 2] and filled[0] > 0 and filled[-1] > 0 and (filled <= case["sizes"]).all()
+    assert sorted(np.unique(case["sizes"]).tolist()) == [0, 1, 2]
+    return case, kw, want
+
+
+def check_most_frames(dev, other_dev=None):
+    """B = 65535 frames, the most a launch takes in its grid's z extent; no map holds anything but depths of its own frame"""
+    case, kw, want = most_frames_case()
+    got = run(case, dev, **kw)
+    check_equal(got, want, "65535 frames")
+    depth, z = got.depth.cpu().numpy().reshape(-1, 4), case["points"][:, :, 2]
+    own = (depth == 0) | ((depth[:, :, None] == z[:, None, :]) & (np.arange(2) < case["sizes"][:, None])[:, None, :]).any(2)
+    assert own.all() and bool((got.bins.cpu().numpy().reshape(-1, 4)[depth == 0] == -1).all())
+    if other_dev is not None:
+        other = run(case, other_dev, **kw)
+        assert torch.equal(got.depth.cpu().view(torch.int32), other.depth.cpu().view(torch.int32)) and torch.equal(got.bins.cpu(), other.bins.cpu())
 
 
 def check_guard_bands(dev, band_cells):

@@ -2,7 +2,7 @@
 definition and the float64 evaluation of depth_targets_cases.py — ragged point counts, every camera / channel / row count,
 both size dtypes, hostile filler, extents and strides that do not divide, every band split, the automatic two-band split,
 hand-placed points at every edge of the definition, bins, image_transforms against camera_augment_boxes' matrices, guard
-bands through the C entry alone, reproducibility, errors and empty inputs."""
+bands through the C entry alone, reproducibility, errors, empty inputs and the largest batch (65535 frames)."""
 import os
 import sys
 
@@ -60,6 +60,10 @@ def test_no_frames_no_points_and_clamped_sizes():
 
 def test_guard_bands_and_complete_write_through_the_c_entry_alone():
     cases.check_guard_bands(DEV, nat.DT_BAND_CELLS)
+
+
+def test_most_frames_a_call_takes():
+    cases.check_most_frames(DEV)
 
 
 def test_every_documented_error():

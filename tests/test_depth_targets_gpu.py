@@ -2,7 +2,7 @@
 depth_targets_cases.py and against the host entry on the same inputs — the cases of test_depth_targets_cpu.py on the device,
 the edges of the kernel's point loop (a workgroup's T lanes, one step of T * U points), GPU against CPU tensors bit for bit,
 guard bands through the C entry alone for 16-byte and 4-byte stores, reproducibility, a non-default stream, errors before
-any launch and empty inputs."""
+any launch, empty inputs and B = 65535 frames, the limit of the grid's z extent."""
 import os
 import re
 import sys
@@ -73,6 +73,11 @@ def test_no_frames_no_points_and_clamped_sizes():
 
 def test_guard_bands_and_complete_write_through_the_c_entry_alone():
     cases.check_guard_bands(DEV, nat.DT_BAND_CELLS)
+
+
+def test_most_frames_a_call_takes():
+    """B = 65535 is gridDim.z of the launch; the same batch on CPU tensors gives the same bits"""
+    cases.check_most_frames(DEV, other_dev="cpu")
 
 
 def test_every_documented_error_is_raised_before_a_launch():

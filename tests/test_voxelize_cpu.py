@@ -2,7 +2,8 @@
 restatement of the loop in voxelize_cases.py, bit for bit on all five outputs — random configurations, the sizes of the
 device's work partition, truncation by max_points and max_voxels (mmcv's `continue` rule), table sizes, hand-placed points at
 every edge of the definition, augmentation rows, concatenate_voxels, guard bands through the C entry alone, errors and empty
-inputs."""
+inputs; and the cases that enter the launch regimes of the device (many chunks, large index lists, max_voxels and
+max_points at their crossings, wide rows, a grid of 2^30 cells, 65535 frames), which pin the host entry at the same inputs."""
 import os
 import sys
 
@@ -83,3 +84,39 @@ def test_guard_bands_and_complete_write_through_the_c_entry_alone():
 
 def test_every_documented_error():
     cases.check_errors(DEV, other_dev="meta")
+
+
+# the regimes of the device's work partition, with its constants as literals: 1024 lanes x 4 points a chunk, 65536 list
+# words a filling workgroup, at most 64 of those a frame
+def test_prefix_over_130_chunks():
+    cases.check_many_chunks(DEV, 130, 1024, 4)
+
+
+def test_prefix_over_1025_chunks():
+    cases.check_many_chunks(DEV, 1025, 1024, 4)
+
+
+def test_lists_of_more_than_one_filling_workgroup():
+    cases.check_list_fill(DEV, 65536, 64)
+
+
+def test_max_voxels_crossed_inside_a_lane_between_waves_and_between_chunks():
+    cases.check_budget_crossings(DEV, 4, 4096)
+
+
+@pytest.mark.parametrize("T", [1, 2, 128])
+def test_voxels_of_max_points_minus_one_to_plus_one_points(T):
+    cases.check_point_budget(DEV, T)
+
+
+@pytest.mark.parametrize("D", [6, 8, 12, 15, 16])
+def test_row_widths_with_and_without_rows_and_off_a_16_byte_boundary(D):
+    cases.check_row_widths(DEV, D)
+
+
+def test_grid_of_two_to_the_thirty_cells():
+    cases.check_large_keys(DEV)
+
+
+def test_most_frames_a_call_takes():
+    cases.check_most_frames(DEV)

@@ -6,7 +6,12 @@ points in slot order with a dict from key to voxel number.  `stop_when_full=True
 the current one has `continue`), which the truncation test asserts to differ.  `augment` restates augment_center of
 csrc/bev_augment_arith.h.  Nothing in the operator is approximate: every comparison is bit for bit, floats as int32 views, so
 that NaN payloads and the sign of zero count.
+
+The second half of the checks enters the launch regimes of csrc/voxelize.hip (DESIGN, "Launch regimes and the tests that
+enter them"); the constants of the device's work partition are arguments, which the GPU file reads from the source.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -444,3 +449,269 @@ def check_errors(dev, other_dev=None):
             call(augmentation=torch.zeros((2, 7), device=other_dev))
         with pytest.raises(RuntimeError, match="device"):
             call(p=RaggedBatch(rb().tensor, sample_sizes=rb().sample_sizes.to(other_dev)))
+
+
+# ------------------------------------------------------------------- the launch regimes of the device's work partition
+# Each check below enters a regime of csrc/voxelize.hip that the checks above leave alone, and asserts through the
+# definition alone that it does: a seed edited later cannot quietly empty the case.
+WAVE = 64
+
+
+def cell_centres(cells, side, cell):
+    """float32 [n, 2]: the centres of the cells (index c_y * side + c_x) of a side x side grid over RANGE; exact in float32"""
+    cells = np.asarray(cells)
+    return ((np.stack([cells % side, cells // side], axis=1) + 0.5) * cell - 4.0).astype(f32)
+
+
+@functools.lru_cache(maxsize=None)
+def many_chunks_case(chunks, scan_points, seed):
+    """one frame of chunks * scan_points + 1 points in which few points open a voxel, so that the voxel number of an opener
+    is the prefix over the chunks before its own: about 70 % of the points are out of range (z = 5), the others sit in 8
+    pillars of row 0 of FINE that the frame's first 8 points open, but for k_c in {0, 1, 2, 3} points of chunk c and the
+    single point of the last chunk, each alone in a cell of rows 1..63.  max_voxels refuses the last five of them; `free`
+    is the definition of the same frame with room for all.
+    Returns (points, sizes, kw, want, free, openers per chunk): built once for both test files, never written to"""
+    rng = np.random.default_rng(seed)
+    P = chunks * scan_points + 1
+    k = rng.integers(0, 4, chunks + 1)
+    k[-1] = 1
+    total = int(k.sum())
+    assert total <= 63 * 64, "more openers than cells in rows 1..63"
+    pts = np.zeros((1, P, 3), f32)
+    pts[0, :, :2] = cell_centres(rng.integers(0, 8, P), 64, 0.125)
+    pts[0, :, 2] = np.where(rng.random(P) < 0.7, f32(5.0), f32(0.0))
+    pts[0, :8, :2], pts[0, :8, 2] = cell_centres(np.arange(8), 64, 0.125), 0.0
+    where = np.concatenate([c * scan_points + 8 + np.sort(rng.choice(scan_points - 8, int(k[c]), replace=False)) for c in range(chunks)]
+                           + [np.array([P - 1])]).astype(np.int64)
+    pts[0, where, :2], pts[0, where, 2] = cell_centres(64 + rng.permutation(63 * 64)[:total], 64, 0.125), 0.0
+    kw = dict(max_points=3, max_voxels=total + 8 - 5, **FINE)
+    want, free = definition(pts, (P,), **kw), definition(pts, (P,), **dict(kw, max_voxels=total + 8))
+    # the case is what its comment says, by the definition alone
+    pv, pv_free = want["point_voxel"][0], free["point_voxel"][0]
+    assert int(free["voxel_counts"][0]) == total + 8 and int(want["voxel_counts"][0]) == total + 3
+    assert np.array_equal(pv_free[where], 8 + np.arange(total)), "an opener's number is not 8 + the openers before it"
+    assert np.array_equal(pv[where[:-5]], 8 + np.arange(total - 5)) and (pv[where[-5:]] == -1).all()
+    refused = np.flatnonzero((pv_free >= 0) & (pv < 0))
+    assert refused.size == 5 and (refused // scan_points >= chunks - 4).all(), "the refusals are not five points of the last chunks"
+    per_chunk = np.bincount(where // scan_points, minlength=chunks + 1)
+    assert np.array_equal(per_chunk, k) and (k == 0).any() and (k == 3).any()
+    return pts, (P,), kw, want, free, per_chunk
+
+
+MANY_CHUNKS_SEEDS = {130: 1, 1025: 5}
+
+
+def check_many_chunks(dev, chunks, scan_threads, unroll):
+    """the numbering workgroup's sum over the chunks before its own: lane i reads the counts of chunks i, i + scan_threads,
+    ...; a wave's lanes are added by shuffles and the waves' sums through LDS.  With more than 2 * 64 chunks in front of
+    the last workgroup waves 1 and 2 carry a value; with more than scan_threads, lane 0 takes a second trip.
+
+    Only the last workgroup (one point, the last opener) reads the count of chunk scan_threads, and a chunk opens at most 3
+    voxels: with the last five openers refused, a sum that misses that count still refuses the last opener and still
+    reports max_voxels voxels.  So the frame is also run with room for every voxel, where the last opener's number and
+    voxel_counts are the whole sum"""
+    pts, sizes, kw, want, free, per_chunk = many_chunks_case(chunks, scan_threads * unroll, MANY_CHUNKS_SEEDS[chunks])
+    assert chunks > 2 * WAVE
+    for w in range(1, -(-chunks // WAVE)):
+        if w * WAVE < scan_threads:
+            assert per_chunk[w * WAVE: min((w + 1) * WAVE, chunks, scan_threads)].sum() > 0, f"wave {w} of the last workgroup carries nothing"
+    if chunks > scan_threads:        # the counts that only a second trip reads: those of chunks scan_threads .. chunks - 1
+        assert per_chunk[scan_threads: chunks].sum() > 0 and per_chunk[scan_threads:].sum() > 1, "the second trip carries nothing"
+    check_equal(run(pts, sizes, dev, **kw), want, f"{chunks} chunks")
+    roomy = dict(kw, max_voxels=int(free["voxel_counts"][0]))
+    assert roomy["max_voxels"] == kw["max_voxels"] + 5 == 8 + int(per_chunk.sum())
+    check_equal(run(pts, sizes, dev, **roomy), free, f"{chunks} chunks, room for all")
+
+
+LIST_FILL_SIZES = (1500, 0, 700)
+
+
+def list_fill_cases(list_words, fill_blocks_max):
+    """(V, T) with more than one list-filling workgroup a frame (list_words index words each), and the workgroups each takes"""
+    out = [(list_words // 3 + 1, 3), (list_words + 1, 1), (2 * list_words // 128 + 1, 128)]
+    blocks = [-(-V * T // list_words) for V, T in out]
+    B = len(LIST_FILL_SIZES)
+    assert blocks == [2, 2, 3] and max(blocks) < fill_blocks_max and [B * V * T % 4 for V, T in out] == [2, 3, 0]
+    return out
+
+
+def list_fill_points(seed, V, T):
+    pts = random_points(seed, LIST_FILL_SIZES, 5)
+    kw = dict(max_points=T, max_voxels=V, **FINE)
+    want = definition(pts, LIST_FILL_SIZES, **kw)
+    counts = want["voxel_counts"].tolist()
+    assert 800 < counts[0] < min(V, 1000) and counts[1] == 0 and 400 < counts[2] < 500, counts
+    assert 4 * int(want["num_points"].sum()) < V * T, "most list words are not left empty"
+    return pts, kw, want
+
+
+def check_padding(got, sizes):
+    """the padding of every output, spelled out: rows from num_points on are +0.0, voxels from voxel_counts on have +0.0
+    rows, coors of -1 and no points, points from sample_sizes on have no voxel"""
+    voxels, coors, num = bits_of(got.voxels), got.coors.cpu(), got.num_points.cpu()
+    B, V, T, _ = voxels.shape
+    for b, n in enumerate(got.voxel_counts.tolist()):
+        assert not voxels[b, n:].any() and bool((coors[b, n:] == -1).all()) and not num[b, n:].any(), f"padding of frame {b}"
+        assert bool((coors[b, :n] >= 0).all()) and bool((num[b, :n] >= 1).all())
+        assert bool((got.point_voxel[b, sizes[b]:] == -1).all())
+    beyond = torch.arange(T).view(1, 1, T) >= num.view(B, V, 1)
+    assert not voxels[beyond].any(), "a row from num_points on is not +0.0"
+
+
+def check_list_fill(dev, list_words, fill_blocks_max):
+    """V * T above the index words one list-filling workgroup takes: two and three of them a frame, dealt over all frames'
+    lists as one range, with the 4-byte tail of that range (B * V * T no multiple of 4)"""
+    for n, (V, T) in enumerate(list_fill_cases(list_words, fill_blocks_max)):
+        pts, kw, want = list_fill_points(300 + n, V, T)
+        got = run(pts, LIST_FILL_SIZES, dev, **kw)
+        check_equal(got, want, f"V {V}, T {T}")
+        check_padding(got, LIST_FILL_SIZES)
+
+
+def check_list_fill_workspace(dev, list_words, fill_blocks_max):
+    """the same through the C entry alone, twice into one workspace of the test's own that starts as zero bytes: a list word
+    that the fill leaves out then reads as point 0, a valid index, and shows as a mismatch; the second call (other points)
+    finds the lists of the first"""
+    import ctypes
+
+    from accvlab import _amd_native as nat
+
+    lib = nat.ctypes_lib()
+    assert torch.device(dev).type == "cuda"
+    B, D = len(LIST_FILL_SIZES), 5
+    for n, (V, T) in enumerate(list_fill_cases(list_words, fill_blocks_max)):
+        P = max(LIST_FILL_SIZES)
+        need = lib.accv_voxelize_workspace_bytes(B, P, V, T, 0)
+        assert need > 0 and need % 16 == 0
+        workspace = torch.zeros((need,), dtype=torch.uint8, device=dev)
+        assert workspace.data_ptr() % 16 == 0
+        stream = nat.stream_ptr(torch.device(dev, torch.cuda.current_device()))
+        for call, seed in enumerate((300 + n, 310 + n)):
+            pts, kw, want = list_fill_points(seed, V, T)
+            rb = ragged(pts, LIST_FILL_SIZES, dev)
+            shapes = dict(voxels=(B, V, T, D), coors=(B, V, 3), num_points=(B, V), voxel_counts=(B,), point_voxel=(B, P))
+            outs = {name: torch.full((4 * int(np.prod(shape)),), 0xA5, dtype=torch.uint8, device=dev)
+                    .view(torch.float32 if name == "voxels" else torch.int32).view(shape) for name, shape in shapes.items()}
+            p = nat.VoxelizeParams()
+            p.points, p.sample_sizes, p.sizes_i64 = rb.tensor.data_ptr(), rb.sample_sizes.data_ptr(), 1
+            p.voxel_size[:], p.range_min[:], p.range_max[:] = FINE["voxel_size"], RANGE[:3], RANGE[3:]
+            p.max_points, p.max_voxels = T, V
+            status = lib.accv_voxelize(ctypes.addressof(p), B, P, D, *(outs[name].data_ptr() for name in FIELDS),
+                                       workspace.data_ptr(), need, stream)
+            torch.cuda.synchronize()
+            assert status == 0, lib.accv_last_error()
+            got = Voxels(**outs)
+            check_equal(got, want, f"V {V}, T {T}, call {call} into a workspace of zero bytes")
+            check_padding(got, LIST_FILL_SIZES)
+
+
+def check_budget_crossings(dev, unroll, scan_points):
+    """max_voxels reached inside a lane's `unroll` consecutive points, between two lanes, between two waves and between
+    two chunks of the numbering launch: every point of frame 0 opens a voxel, so voxel V is refused at point V"""
+    side, extra = 128, 300
+    P = scan_points + extra
+    rng = np.random.default_rng(12)
+    pts = np.zeros((2, P, 3), f32)
+    pts[0, :, :2] = cell_centres(rng.permutation(side * side)[:P], side, 0.0625)
+    pts[1, :extra, :2] = cell_centres(rng.permutation(side * side)[:extra], side, 0.0625)
+    sizes = (P, extra)
+    budgets = sorted(set(range(1, unroll + 2)) | {n + d for n in (WAVE * unroll, scan_points) for d in (-1, 0, 1)})
+    assert len(budgets) == unroll + 7 and budgets[-1] < P
+    for V in budgets:
+        kw = dict(max_points=1, max_voxels=V, voxel_size=(0.0625, 0.0625, 4.0), point_cloud_range=RANGE)
+        want = definition(pts, sizes, **kw)
+        assert want["voxel_counts"].tolist() == [V, min(V, extra)]
+        assert np.array_equal(want["point_voxel"][0, :V], np.arange(V)) and (want["point_voxel"][0, V:] == -1).all()
+        check_equal(run(pts, sizes, dev, **kw), want, f"max_voxels {V}")
+
+
+def check_point_budget(dev, T):
+    """voxels that receive T - 1, T, T + 1 and 8 T points and one point, interleaved, in one frame and in its reverse: the
+    end of the rank cascade and the rule that finds a voxel's last row"""
+    groups = ([T - 1] if T > 1 else []) + [T, T + 1, 8 * T, 1]
+    rng = np.random.default_rng(40 + T)
+    label = rng.permutation(np.repeat(np.arange(len(groups)), groups))
+    P = label.size
+    cells = rng.permutation(256)[:len(groups)]
+    pts = np.zeros((2, P, 4), f32)
+    pts[0, :, :2] = cell_centres(cells[label], 16, 0.5) + rng.uniform(-0.2, 0.2, (P, 2)).astype(f32)
+    pts[0, :, 2] = rng.uniform(-1.9, 1.9, P)
+    pts[1] = pts[0, ::-1]
+    pts[:, :, 3] = np.arange(P)
+    kw = dict(max_points=T, max_voxels=2 * len(groups), **PILLARS)
+    want = definition(pts, (P, P), **kw)
+    assert want["voxel_counts"].tolist() == [len(groups)] * 2
+    for b, lab in enumerate((label, label[::-1])):
+        for g, n in enumerate(groups):
+            idx = np.flatnonzero(lab == g)
+            assert idx.size == n and (n < 2 or int(np.diff(idx).max()) > 1), "the points of a voxel are contiguous"
+            v = int(want["point_voxel"][b, idx[0]])
+            kept = min(n, T)
+            assert v >= 0 and (want["point_voxel"][b, idx] == v).all(), "a point beyond max_points lost its voxel"
+            assert int(want["num_points"][b, v]) == kept
+            assert want["voxels"][b, v, :kept, 3].tolist() == idx[:kept].tolist(), "not the T lowest indices in ascending order"
+            assert not want["voxels"][b, v, kept:].view(np.uint32).any()
+    check_equal(run(pts, (P, P), dev, **kw), want, f"max_points {T}")
+
+
+def run_misaligned(pts, sizes, dev, augmentation=None, **kw):
+    """`run` with the first point 4 bytes off a 16-byte boundary"""
+    flat = torch.zeros(pts.size + 1, dtype=torch.float32, device=dev)
+    view = flat[1:].view(pts.shape)
+    view.copy_(torch.from_numpy(pts))
+    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+    aug = None if augmentation is None else torch.from_numpy(np.asarray(augmentation, f32)).to(dev)
+    return voxelize_points(RaggedBatch(view, sample_sizes=torch.tensor(sizes, device=dev)), augmentation=aug, return_point_voxel=True, **kw)
+
+
+def check_row_widths(dev, D):
+    """rows of 6, 8, 12, 15 and 16 channels, with and without augmentation rows; the multiples of 4 also off a 16-byte
+    boundary, where the gather goes element by element"""
+    sizes = (700, 257)
+    pts = random_points(500 + D, sizes, D)
+    kw = dict(max_points=3, max_voxels=150, **VOXELS3D)
+    for aug in (None, rows(D, 2)):
+        what = f"D {D}, {'rows' if aug is not None else 'no rows'}"
+        want = definition(pts, sizes, augmentation=aug, **kw)
+        assert int(want["voxel_counts"][0]) == 150 and 100 < int(want["voxel_counts"][1]) <= 150
+        stored = want["voxels"][want["num_points"] > 0][:, 0]
+        assert np.isnan(stored[:, -1]).any() and np.isnan(stored[:, 3]).any(), "no NaN payload rides in a stored row's last channel"
+        check_equal(run(pts, sizes, dev, augmentation=aug, **kw), want, what)
+        if D % 4 == 0:
+            check_equal(run_misaligned(pts, sizes, dev, augmentation=aug, **kw), want, what + ", misaligned")
+
+
+def check_large_keys(dev):
+    """a grid of 2^30 cells (2048 x 1024 x 512): keys, probe starts and coors near the largest key"""
+    kw = dict(max_points=3, max_voxels=2000, voxel_size=(2.0 ** -8, 2.0 ** -7, 2.0 ** -7), point_cloud_range=RANGE)
+    rng = np.random.default_rng(60)
+    sizes = (1500,)
+    pts = random_points(61, sizes, 4, spread=4.2)
+    pts[0, :, 2] = rng.uniform(-2.1, 2.1, 1500)
+    pts[0, :40, :3] = np.array([4.0, 4.0, 2.0]) - rng.uniform(0.0, 0.02, (40, 3))
+    pts[0, 0, :3] = (4.0 - 2.0 ** -9, 4.0 - 2.0 ** -8, 2.0 - 2.0 ** -8)        # the centre of the last cell
+    want = definition(pts, sizes, **kw)
+    n = int(want["voxel_counts"][0])
+    c = want["coors"][0, :n].astype(np.int64)
+    keys = (c[:, 0] * 1024 + c[:, 1]) * 2048 + c[:, 2]
+    assert 1000 < n < 1500 and tuple(c.max(0)) == (511, 1023, 2047)
+    assert int(keys.max()) == 2 ** 30 - 1 and int((keys > 2 ** 29).sum()) > 100 and int(np.unique(keys).size) == n
+    check_equal(run(pts, sizes, dev, **kw), want, "2^30 cells")
+
+
+@functools.lru_cache(maxsize=None)
+def most_frames_case():
+    B = 65535
+    sizes = np.random.default_rng(70).integers(0, 3, B)
+    pts = random_points(71, (2,) * B, 3, spread=4.2)
+    kw = dict(max_points=1, max_voxels=2, **PILLARS)
+    want = definition(pts, sizes, **kw)
+    assert sorted(np.unique(want["voxel_counts"]).tolist()) == [0, 1, 2] and int(want["voxel_counts"][-1]) > 0
+    assert sorted(np.unique(sizes).tolist()) == [0, 1, 2]
+    return pts, sizes, kw, want
+
+
+def check_most_frames(dev):
+    """B = 65535 frames, the most a launch takes in its grid's y extent"""
+    pts, sizes, kw, want = most_frames_case()
+    check_equal(run(pts, sizes, dev, **kw), want, "65535 frames")
