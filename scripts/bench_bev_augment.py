@@ -19,20 +19,12 @@ ONE JSON line.
 
     python3 scripts/bench_bev_augment.py [--warmup 20] [--iters 200] [--calls 50] [--out FILE]
 """
-import argparse
 import json
 import math
-import os
-import statistics
-import sys
-import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, round_trips, shown, summary, window_times
 
 RANGE = ((-51.2, -51.2, -5.0), (51.2, 51.2, 3.0))
 BARS = dict(boxes=5, point=9, frame=5)
@@ -138,60 +130,6 @@ def differing(got, ref, inputs):
     return bad
 
 
-def timed(fns, warmup, iters, calls):
-    """per-call ms of every callable: `iters` windows of `calls` back-to-back calls each, the sides alternating window by
-    window; median and minimum over the windows, and the time all windows of a side took together"""
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    events = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(calls):
-                f()
-            b.record()
-            events[k].append((a, b))
-        torch.cuda.synchronize()          # keep the queue short: a window must not wait behind the other side's backlog
-    ms = {k: [a.elapsed_time(b) / calls for a, b in v] for k, v in events.items()}
-    return {k: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), timed_s=round(sum(v) * calls / 1e3, 3))
-            for k, v in ms.items()}
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        kernels = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                   and not e.name.lower().startswith(("memcpy", "memset"))]
-        return len(kernels) or None
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
-def round_trips(f):
-    """synchronising calls in one call of f, as torch's sync debug mode reports them"""
-    f()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            f()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    return sum("synchroniz" in str(w.message).lower() for w in caught)
-
-
 def workload(B, args, dev):
     from accvlab.batching_helpers import RaggedBatch
     from accvlab.draw_heatmap import bev_augment_boxes
@@ -207,15 +145,14 @@ def workload(B, args, dev):
     ref = composition(boxes.double(), labels, valid, sizes, rows.double(), {n: m.double() for n, m in mats.items()}, k)
     torch.cuda.synchronize()
     bad = differing(got, ref, (boxes, p_in, (mats["world_to_ego"],)))
-    ms = timed({"fused": fused, "torch": comp}, args.warmup, args.iters, args.calls)
+    ms = {k: summary(v, args.calls) for k, v in window_times({"fused": fused, "torch": comp}, args.warmup, args.iters, args.calls).items()}
     n = {"fused": launches(fused), "torch": launches(comp)}
-    trips = {"fused": round_trips(fused), "torch": round_trips(comp)}
-    show = lambda v: v if v is not None else "not measured"   # noqa: E731
+    trips = {"fused": shown(round_trips(fused)), "torch": shown(round_trips(comp))}
     result = dict(shape=dict(B=B, N=int(boxes.shape[1]), D=9, point_transforms=[list(m.shape) for m in p_in],
                              frame_transforms=[list(mats["world_to_ego"].shape)]),
                   objects=int(sizes.sum()), kept=int(got.boxes.sample_sizes.sum()), fused=ms["fused"], torch=ms["torch"],
                   speedup_median=round(ms["torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
-                  launches_fused=show(n["fused"]), launches_torch=show(n["torch"]), host_round_trips_fused=trips["fused"],
+                  launches_fused=shown(n["fused"]), launches_torch=shown(n["torch"]), host_round_trips_fused=trips["fused"],
                   host_round_trips_torch=trips["torch"], tensors_beyond_the_bar=bad)
     lines = [f"bev_augment_boxes  B={B} N<={boxes.shape[1]} D=9, 3 point transforms (6 + 6 + 1 matrices per frame), 1 frame transform: "
              f"{int(sizes.sum())} objects, {result['kept']} kept",
@@ -229,17 +166,11 @@ def workload(B, args, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=200, help="timed windows per side")
-    ap.add_argument("--calls", type=int, default=50, help="back-to-back calls per window")
+    ap = parser(warmup=20, iters=200, calls=50)
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 4])
     ap.add_argument("--n-max", type=int, default=128)
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_bev_augment.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", 0)
+    dev = gpu()
     results, lines = [], []
     for B in args.batches:
         r, ls = workload(B, args, dev)
@@ -248,10 +179,7 @@ def main():
     first = results[0]
     lines.append(json.dumps(dict(metric="bev_augment_boxes_ms", unit="ms", value=first["fused"]["median_ms"], warmup=args.warmup,
                                  iters=args.iters, calls_per_window=args.calls, workloads=results)))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

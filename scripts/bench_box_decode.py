@@ -24,20 +24,12 @@ Prints a few lines of log per K and ONE JSON line.
 
     python3 scripts/bench_box_decode.py [--warmup 20] [--iters 10] [--calls 10] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
-import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, round_trips, shown, summary, window_times
 
 FRAMES, CATEGORIES = 48, 10
 HM, WM = 112, 200
@@ -109,78 +101,14 @@ def composition(heat, heads, K):
     return out_boxes, out_scores, out_labels, out_source, sizes.to(dev)
 
 
-def timed(fns, warmup, iters, calls):
-    """per-call ms of every callable: `iters` blocks of `calls` back-to-back calls each, the sides alternating block by
-    block; median and minimum over the blocks, and the time all blocks of a side took together"""
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    events = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(calls):
-                f()
-            b.record()
-            events[k].append((a, b))
-        torch.cuda.synchronize()
-    ms = {k: [a.elapsed_time(b) / calls for a, b in v] for k, v in events.items()}
-    return {k: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), max_ms=round(max(v), 5), timed_s=round(sum(v) * calls / 1e3, 3))
-            for k, v in ms.items()}
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        kernels = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                   and not e.name.lower().startswith(("memcpy", "memset"))]
-        return len(kernels) or None
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
-def round_trips(f):
-    """synchronisations of the host with the device in one call, or None when the debug mode cannot tell"""
-    try:
-        f()
-        torch.cuda.synchronize()
-        torch.cuda.set_sync_debug_mode("warn")
-        try:
-            with warnings.catch_warnings(record=True) as seen:
-                warnings.simplefilter("always")
-                f()
-        finally:
-            torch.cuda.set_sync_debug_mode("default")
-        torch.cuda.synchronize()
-        return sum("synchroniz" in str(w.message).lower() for w in seen)
-    except Exception:   # pragma: no cover - builds differ
-        return None
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=10, help="timed blocks per side")
-    ap.add_argument("--calls", type=int, default=10, help="back-to-back calls per block")
+    ap = parser(warmup=20, iters=10, calls=10)
     ap.add_argument("--k", type=int, nargs="+", default=[100, 500])
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_box_decode.py measures on a GPU; none is visible")
+    dev = gpu()
     from accvlab.draw_heatmap import box_heatmap_decode, heatmap_peaks
 
-    dev = torch.device("cuda", 0)
     heat, heads = make_inputs(dev)
-    show = lambda n: n if n is not None else "not measured"   # noqa: E731
     lines, results = [], []
     for K in args.k:
         def fused():
@@ -196,31 +124,29 @@ def main():
         differ = sum(0 if a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)) else 1
                      for a, b in zip(mine, ref))
         dets = int(got.boxes.sample_sizes.sum())
-        ms = timed({"fused": fused, "decode_only": decode_only, "torch": comp}, args.warmup, args.iters, args.calls)
+        ms = window_times({"fused": fused, "decode_only": decode_only, "torch": comp}, args.warmup, args.iters, args.calls)
+        ms = {k: summary(v, args.calls, with_max=True) for k, v in ms.items()}
         n_fused, n_decode, n_torch = launches(fused), launches(decode_only), launches(comp)
         r_fused, r_decode, r_torch = round_trips(fused), round_trips(decode_only), round_trips(comp)
         results.append(dict(K=K, detections=dets, fused=ms["fused"], decode_only=ms["decode_only"], torch=ms["torch"],
                             speedup_median=round(ms["torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
-                            launches_fused=show(n_fused), launches_decode_only=show(n_decode), launches_torch=show(n_torch),
-                            host_round_trips_fused=show(r_fused), host_round_trips_decode_only=show(r_decode),
-                            host_round_trips_torch=show(r_torch), output_tensors_that_differ=differ))
+                            launches_fused=shown(n_fused), launches_decode_only=shown(n_decode), launches_torch=shown(n_torch),
+                            host_round_trips_fused=shown(r_fused), host_round_trips_decode_only=shown(r_decode),
+                            host_round_trips_torch=shown(r_torch), output_tensors_that_differ=differ))
         lines += [f"box_heatmap_decode  F={FRAMES} C={CATEGORIES} {HM}x{WM} K={K} post_max_size={OPTS['post_max_size']}: {dets} detections",
                   f"  {args.warmup} warm-up calls, {args.iters} blocks of {args.calls} calls per side, alternating; timed {ms['fused']['timed_s']} s "
                   f"fused, {ms['torch']['timed_s']} s torch",
-                  f"  peaks + decode  median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {show(n_fused)}  "
-                  f"host round trips {show(r_fused)}",
+                  f"  peaks + decode  median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {shown(n_fused)}  "
+                  f"host round trips {shown(r_fused)}",
                   f"  decode alone    median {ms['decode_only']['median_ms']:.4f} ms  min {ms['decode_only']['min_ms']:.4f} ms  launches "
-                  f"{show(n_decode)}  host round trips {show(r_decode)}",
-                  f"  torch + host    median {ms['torch']['median_ms']:.4f} ms  min {ms['torch']['min_ms']:.4f} ms  launches {show(n_torch)}  "
-                  f"host round trips {show(r_torch)}",
+                  f"{shown(n_decode)}  host round trips {shown(r_decode)}",
+                  f"  torch + host    median {ms['torch']['median_ms']:.4f} ms  min {ms['torch']['min_ms']:.4f} ms  launches {shown(n_torch)}  "
+                  f"host round trips {shown(r_torch)}",
                   f"  against the torch composition: {differ} of 5 output tensors differ"]
     result = dict(metric="box_heatmap_decode_ms", unit="ms", value=results[-1]["fused"]["median_ms"], warmup=args.warmup, iters=args.iters,
                   calls_per_block=args.calls, shape=dict(F=FRAMES, C=CATEGORIES, H=HM, W=WM, post_max_size=OPTS["post_max_size"]), runs=results)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

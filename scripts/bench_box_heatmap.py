@@ -24,20 +24,12 @@ Prints a few lines of log per size and ONE JSON line.
 
     python3 scripts/bench_box_heatmap.py [--warmup 20] [--iters 100] [--calls 20] [--baseline-iters 3] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, shown, summary, timed_windows, wall_times
 
 SIZES = ((48, 900, 1600, 112, 200, 64), (64, 1080, 1920, 270, 480, 128))
 CLASSES = 10
@@ -141,51 +133,6 @@ def torch_composition(boxes, cats, sizes, H, W, Hm, Wm):
     return hm.view(B, CLASSES, Hm, Wm), active, center, offset, hw, clipped, radii
 
 
-def timed_windows(f, warmup, iters, calls):
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    events = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            f()
-        b.record()
-        events.append((a, b))
-        torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) / calls for a, b in events]
-    return dict(median_ms=round(statistics.median(ms), 5), min_ms=round(min(ms), 5), timed_s=round(sum(ms) * calls / 1e3, 3))
-
-
-def timed_calls(f, iters):
-    f()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        t = time.perf_counter()
-        f()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t) * 1e3)
-    return dict(median_ms=round(statistics.median(ms), 3), min_ms=round(min(ms), 3), timed_s=round(sum(ms) / 1e3, 3))
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        return len([e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                    and not e.name.lower().startswith(("memcpy", "memset"))])
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
 def differing(got, ref):
     """per output tensor: 1 when it differs from the baseline beyond the bar (the map 1e-5 absolute, the rest bit for bit)"""
     out = {}
@@ -199,20 +146,14 @@ def differing(got, ref):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=100, help="timed windows of the fused side and of the torch baseline")
-    ap.add_argument("--calls", type=int, default=20, help="back-to-back fused calls per window")
+    ap = parser(warmup=20, iters=100, calls=20)
     ap.add_argument("--baseline-calls", type=int, default=2, help="back-to-back torch-baseline calls per window")
     ap.add_argument("--baseline-iters", type=int, default=3, help="timed calls of the numpy baseline")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_box_heatmap.py measures on a GPU; none is visible")
+    dev = gpu()
     from accvlab.batching_helpers import RaggedBatch
     from accvlab.draw_heatmap import boxes_to_heatmap
 
-    dev = torch.device("cuda", 0)
     lines, results = [], []
     for B, H, W, Hm, Wm, n_max in SIZES:
         boxes, cats, sizes = make_inputs(B, H, W, n_max, dev)
@@ -233,9 +174,8 @@ def main():
         map_err = dict(numpy=float((got[0] - ref_np[0]).abs().max()), torch=float((got[0] - ref_t[0]).abs().max()))
         ms = dict(fused=timed_windows(fused, args.warmup, args.iters, args.calls),
                   torch=timed_windows(via_torch, 3, args.iters, args.baseline_calls),
-                  numpy=timed_calls(via_numpy, args.baseline_iters))
-        n = {k: launches(f) for k, f in (("fused", fused), ("torch", via_torch))}
-        n = {k: v if v is not None else "not measured" for k, v in n.items()}
+                  numpy=summary(wall_times(via_numpy, args.baseline_iters), digits=3))
+        n = {k: shown(launches(f)) for k, f in (("fused", fused), ("torch", via_torch))}
         n["numpy"] = 0                                            # copies only, by construction
         trips = dict(fused=0, torch=0, numpy=2)
         res = dict(shape=dict(B=B, H=H, W=W, map_h=Hm, map_w=Wm, N=int(boxes.shape[1]), classes=CLASSES), boxes=int(sizes.sum()),
@@ -260,10 +200,7 @@ def main():
                   iters=args.iters, calls_per_window=args.calls, baseline_calls_per_window=args.baseline_calls,
                   baseline_iters=args.baseline_iters, sizes=results)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

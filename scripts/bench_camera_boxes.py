@@ -22,19 +22,11 @@ the operator around them.
 
     python3 scripts/bench_camera_boxes.py [--warmup 20] [--iters 200] [--calls 50] [--entry-only] [--out FILE]
 """
-import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "scripts")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
-
-from bench_bev_augment import launches, round_trips, timed  # noqa: E402
+from measure import emit, gpu, launches, parser, round_trips, shown, summary, timed_windows, window_times
 
 WORKLOADS = ((48, 64), (64, 128))
 SOURCE_HW, OUTPUT_HW = (900, 1600), (256, 704)
@@ -158,14 +150,13 @@ def workload(Fr, n_max, args, dev):
     mats64 = composition(boxes.double(), centers.double(), depths, cats, sizes, t.double(), tuple(m.double() for m in mats), hw)[3]
     torch.cuda.synchronize()
     bad = differing(got, ref, mats64, (boxes, centers, mats, t))
-    ms = timed({"fused": fused, "torch": comp}, args.warmup, args.iters, args.calls)
+    ms = {k: summary(v, args.calls) for k, v in window_times({"fused": fused, "torch": comp}, args.warmup, args.iters, args.calls).items()}
     n = {"fused": launches(fused), "torch": launches(comp)}
-    trips = {"fused": round_trips(fused), "torch": round_trips(comp)}
-    show = lambda v: v if v is not None else "not measured"   # noqa: E731
+    trips = {"fused": shown(round_trips(fused)), "torch": shown(round_trips(comp))}
     result = dict(shape=dict(F=Fr, G=int(boxes.shape[1]), image_hw=list(hw), projection_matrices=[list(m.shape) for m in mats]),
                   boxes=int(sizes.sum()), visible=int(got.visible.tensor.sum()), kept=int(got.bboxes.sample_sizes.sum()),
                   fused=ms["fused"], torch=ms["torch"], speedup_median=round(ms["torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
-                  launches_fused=show(n["fused"]), launches_torch=show(n["torch"]), host_round_trips_fused=trips["fused"],
+                  launches_fused=shown(n["fused"]), launches_torch=shown(n["torch"]), host_round_trips_fused=trips["fused"],
                   host_round_trips_torch=trips["torch"], tensors_beyond_the_bar=bad)
     lines = [f"camera_augment_boxes  F={Fr} frames, G<={boxes.shape[1]}, {SOURCE_HW[0]}x{SOURCE_HW[1]} -> {hw[0]}x{hw[1]}, occlusion + "
              f"minimum_size {MIN_SIZE:g}, categories, centres, lidar2img [F, 4, 4], intrinsics [F, 3, 3]: {int(sizes.sum())} boxes, "
@@ -208,7 +199,7 @@ def entry_alone(Fr, n_max, args, dev):
     def call():
         assert entry(*cargs) == 0
 
-    ms = timed({"entry": call}, args.warmup, args.iters, args.calls)["entry"]
+    ms = timed_windows(call, args.warmup, args.iters, args.calls)
     torch.cuda.synchronize()
     same = all(torch.equal(a, b) for a, b in zip(want, (out.bboxes.tensor, out.keep.tensor, out.bboxes.sample_sizes)))
     line = (f"accv_camera_boxes alone  F={Fr} frames, G<={boxes.shape[1]}: {args.iters} windows of {args.calls} calls; "
@@ -217,16 +208,10 @@ def entry_alone(Fr, n_max, args, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=200, help="timed windows per side")
-    ap.add_argument("--calls", type=int, default=50, help="back-to-back calls per window")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
+    ap = parser(warmup=20, iters=200, calls=50)
     ap.add_argument("--entry-only", action="store_true", help="time the C entry alone on outputs allocated once, nothing else")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_camera_boxes.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", 0)
+    dev = gpu()
     results, lines = [], []
     if args.entry_only:
         for Fr, n_max in WORKLOADS:
@@ -235,10 +220,7 @@ def main():
             lines += ls
         lines.append(json.dumps(dict(metric="accv_camera_boxes_entry_ms", unit="ms", value=results[0]["entry"]["median_ms"],
                                      warmup=args.warmup, iters=args.iters, calls_per_window=args.calls, workloads=results)))
-        print("\n".join(lines), flush=True)
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write("\n".join(lines) + "\n")
+        emit(lines, args.out)
         return
     for Fr, n_max in WORKLOADS:
         r, ls = workload(Fr, n_max, args, dev)
@@ -246,10 +228,7 @@ def main():
         lines += ls
     lines.append(json.dumps(dict(metric="camera_augment_boxes_ms", unit="ms", value=results[0]["fused"]["median_ms"], warmup=args.warmup,
                                  iters=args.iters, calls_per_window=args.calls, workloads=results)))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
     if any(r["tensors_beyond_the_bar"] for r in results):
         raise SystemExit("the fused call differs from the composition")
 

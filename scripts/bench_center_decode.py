@@ -22,19 +22,12 @@ Prints a few lines of log and ONE JSON line.
 
     python3 scripts/bench_center_decode.py [--warmup 100] [--iters 20] [--calls 100] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, shown, summary, window_times
 
 TASKS = ((0,), (1, 2), (3, 4), (5,), (6, 7), (8, 9))
 MIN_RADIUS = [4, 12, 10, 1, 0.85, 0.175]
@@ -99,59 +92,14 @@ def composition(logits, heads, K):
     return out
 
 
-def timed(fns, warmup, iters, calls):
-    """per-call ms of every callable: `iters` blocks of `calls` back-to-back calls each, the sides alternating block by
-    block; median, minimum and maximum over the blocks, and the time all blocks of a side took together"""
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    events = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(calls):
-                f()
-            b.record()
-            events[k].append((a, b))
-        torch.cuda.synchronize()
-    ms = {k: [a.elapsed_time(b) / calls for a, b in v] for k, v in events.items()}
-    return {k: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), max_ms=round(max(v), 5), timed_s=round(sum(v) * calls / 1e3, 3))
-            for k, v in ms.items()}
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        kernels = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                   and not e.name.lower().startswith(("memcpy", "memset"))]
-        return len(kernels) or None
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--iters", type=int, default=20, help="timed blocks per side")
-    ap.add_argument("--calls", type=int, default=100, help="back-to-back calls per block")
+    ap = parser(warmup=100, iters=20, calls=100)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--k", type=int, default=500)
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_center_decode.py measures on a GPU; none is visible")
+    dev = gpu()
     from accvlab.draw_heatmap import center_point_decode, heatmap_peaks
 
-    dev = torch.device("cuda", 0)
     logits, heads = make_inputs(args.batch, dev)
     K = args.k
 
@@ -176,31 +124,28 @@ def main():
             if n:
                 box_err = max(box_err, float((d.boxes.tensor[b, :n] - bx).abs().max()))
                 score_err = max(score_err, float((d.scores.tensor[b, :n] - sc).abs().max()))
-    ms = timed({"fused": fused, "decode_only": decode_only, "torch": comp}, args.warmup, args.iters, args.calls)
+    ms = window_times({"fused": fused, "decode_only": decode_only, "torch": comp}, args.warmup, args.iters, args.calls)
+    ms = {k: summary(v, args.calls, with_max=True) for k, v in ms.items()}
     n_fused, n_decode, n_torch = launches(fused), launches(decode_only), launches(comp)
-    show = lambda n: n if n is not None else "not measured"   # noqa: E731
     result = dict(metric="center_point_decode_ms", unit="ms", value=ms["fused"]["median_ms"], warmup=args.warmup, iters=args.iters,
                   calls_per_block=args.calls, shape=dict(B=args.batch, T=len(TASKS), H=H, W=W, K=K, post_max_size=OPTS["post_max_size"]),
                   detections=dets, fused=ms["fused"], decode_only=ms["decode_only"], torch=ms["torch"],
                   speedup_median=round(ms["torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
-                  launches_fused=show(n_fused), launches_decode_only=show(n_decode), launches_torch=show(n_torch),
+                  launches_fused=shown(n_fused), launches_decode_only=shown(n_decode), launches_torch=shown(n_torch),
                   host_round_trips_torch=len(TASKS) * args.batch,
                   frames_with_other_count_vs_torch=count_mismatch, label_mismatches_vs_torch=label_mismatch,
                   boxes_max_abs_diff_vs_torch=box_err, scores_max_abs_diff_vs_torch=score_err)
     lines = [f"center_point_decode  B={args.batch} T={len(TASKS)} {H}x{W} K={K} post_max_size={OPTS['post_max_size']}: {dets} detections",
              f"  {args.warmup} warm-up calls, {args.iters} blocks of {args.calls} calls per side, alternating; timed {ms['fused']['timed_s']} s fused, "
              f"{ms['torch']['timed_s']} s torch",
-             f"  peaks + decode  median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {show(n_fused)}",
-             f"  decode alone    median {ms['decode_only']['median_ms']:.4f} ms  min {ms['decode_only']['min_ms']:.4f} ms  launches {show(n_decode)}",
-             f"  torch + host    median {ms['torch']['median_ms']:.4f} ms  min {ms['torch']['min_ms']:.4f} ms  launches {show(n_torch)}  "
+             f"  peaks + decode  median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {shown(n_fused)}",
+             f"  decode alone    median {ms['decode_only']['median_ms']:.4f} ms  min {ms['decode_only']['min_ms']:.4f} ms  launches {shown(n_decode)}",
+             f"  torch + host    median {ms['torch']['median_ms']:.4f} ms  min {ms['torch']['min_ms']:.4f} ms  launches {shown(n_torch)}  "
              f"host round trips {len(TASKS) * args.batch}",
              f"  against the torch composition: {count_mismatch} frames with another count, {label_mismatch} labels differ, boxes max abs diff "
              f"{box_err:.3e}, scores {score_err:.3e}",
              json.dumps(result)]
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

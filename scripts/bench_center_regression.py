@@ -11,18 +11,12 @@ device events; medians.  Prints ONE JSON line.
 
     python3 scripts/bench_center_regression.py [--warmup 10] [--iters 100] [--out FILE] [--cases a_f32,b_f32]
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "tests")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import call_times, emit, gpu, parser   # puts the repository root and tests/ on the path
 
 import bench_workloads as wl  # noqa: E402
 import center_regression_cases as cr  # noqa: E402
@@ -33,27 +27,6 @@ CASES = {
     "b_f32": dict(B=4, H=180, W=180, heads=[2, 1, 3, 2, 2], n_max=500, dtype=torch.float32),
     "c_f32": dict(B=8, H=1080, W=1920, heads=[4], n_max=128, dtype=torch.float32),
 }
-
-
-def timed(fns, warmup, iters):
-    """medians in ms of the callables, run one after the other inside every iteration"""
-    for _ in range(warmup):
-        for f in fns.values():
-            pre = getattr(f, "prepare", None)
-            f(pre()) if pre else f()
-    torch.cuda.synchronize()
-    events = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            pre = getattr(f, "prepare", None)
-            state = pre() if pre else None
-            a.record()
-            f(state) if pre else f()
-            b.record()
-            events[k].append((a, b))
-    torch.cuda.synchronize()
-    return {k: round(statistics.median(a.elapsed_time(b) for a, b in v), 4) for k, v in events.items()}
 
 
 def run_case(name, cfg, dev, warmup, iters):
@@ -99,9 +72,10 @@ def run_case(name, cfg, dev, warmup, iters):
 
     with torch.no_grad():
         lf, lc = float(fused()), float(comp())
-    ms = timed({"fused_fwd_ms": fwd(fused), "torch_fwd_ms": fwd(comp), "fused_fwd_bwd_ms": fwd_bwd(fused),
-                "torch_fwd_bwd_ms": fwd_bwd(comp), "fused_bwd_ms": bwd(fused), "torch_bwd_ms": bwd(comp), "zero_ms": zero},
-               warmup, iters)
+    ms = call_times({"fused_fwd_ms": fwd(fused), "torch_fwd_ms": fwd(comp), "fused_fwd_bwd_ms": fwd_bwd(fused),
+                     "torch_fwd_bwd_ms": fwd_bwd(comp), "fused_bwd_ms": bwd(fused), "torch_bwd_ms": bwd(comp), "zero_ms": zero},
+                    warmup, iters)
+    ms = {k: round(statistics.median(v), 4) for k, v in ms.items()}
     grad_bytes = sum(t.numel() * t.element_size() for t in grads)
     return dict(ms, shape=[B, heads, H, W], dtype=str(dtype).split(".")[-1], n_max=N, objects=int(sizes.sum()),
                 grad_bytes=grad_bytes, speedup_fwd=round(ms["torch_fwd_ms"] / ms["fused_fwd_ms"], 2),
@@ -111,25 +85,16 @@ def run_case(name, cfg, dev, warmup, iters):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--iters", type=int, default=100)
+    ap = parser(warmup=10, iters=100)
     ap.add_argument("--cases", default=",".join(CASES))
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_center_regression.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", 0)
+    dev = gpu()
     result = {"metric": "center_regression_fwd_bwd_ms", "unit": "ms", "warmup": args.warmup, "iters": args.iters}
     for name in args.cases.split(","):
         result[name] = run_case(name, CASES[name], dev, args.warmup, args.iters)
     first = args.cases.split(",")[0]
     result["value"] = result[first]["fused_fwd_bwd_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

@@ -14,19 +14,12 @@ measured" if the profiler is unavailable.  Prints a few lines of log and ONE JSO
 
     python3 scripts/bench_center_targets.py [--warmup 20] [--iters 200] [--calls 50] [--out FILE]
 """
-import argparse
 import json
 import math
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, shown, summary, window_times
 
 TASKS = ((0,), (1, 2), (3, 4), (5,), (6, 7), (8, 9))
 CFG = dict(pc_range=[-54.0, -54.0, -5.0, 54.0, 54.0, 3.0], voxel_size=[0.075, 0.075, 0.2], out_size_factor=8, grid_size=(180, 180),
@@ -102,60 +95,15 @@ def composition(boxes, labels, sizes, k, T, cfg):
             compact(iy.long() * W + ix.long(), 0, torch.int64), compact(slot[None].expand(B, N), -1, torch.int32), kept)
 
 
-def timed(fns, warmup, iters, calls):
-    """per-call ms of every callable: `iters` windows of `calls` back-to-back calls each, the sides alternating window by
-    window; median and minimum over the windows, and the time all windows of a side took together"""
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    events = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(calls):
-                f()
-            b.record()
-            events[k].append((a, b))
-        torch.cuda.synchronize()          # keep the queue short: a window must not wait behind the other side's backlog
-    ms = {k: [a.elapsed_time(b) / calls for a, b in v] for k, v in events.items()}
-    return {k: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), timed_s=round(sum(v) * calls / 1e3, 3))
-            for k, v in ms.items()}
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        kernels = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                   and not e.name.lower().startswith(("memcpy", "memset"))]
-        return len(kernels) or None
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=200, help="timed windows per side")
-    ap.add_argument("--calls", type=int, default=50, help="back-to-back calls per window")
+    ap = parser(warmup=20, iters=200, calls=50)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--n-max", type=int, default=128)
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_center_targets.py measures on a GPU; none is visible")
+    dev = gpu()
     from accvlab.batching_helpers import RaggedBatch
     from accvlab.draw_heatmap import center_point_targets
 
-    dev = torch.device("cuda", 0)
     boxes, labels, sizes = make_inputs(args.batch, args.n_max, dev)
     rb, rl = RaggedBatch(boxes, sample_sizes=sizes), RaggedBatch(labels, sample_sizes=sizes)
     k = constants(CFG, dev)
@@ -168,14 +116,12 @@ def main():
     mismatch = {n: int((torch.stack([getattr(r, n).tensor for r in got]) != ref[i]).sum()) for i, n in enumerate(names) if n != "targets"}
     mismatch["sizes"] = int((torch.stack([r.centers.sample_sizes for r in got]) != ref[6]).sum())
     terr = float((torch.stack([r.targets.tensor for r in got]) - ref[3]).abs().max())
-    ms = timed({"fused": fused, "torch": comp}, args.warmup, args.iters, args.calls)
-    n_fused, n_torch = launches(fused), launches(comp)
+    ms = {k: summary(v, args.calls) for k, v in window_times({"fused": fused, "torch": comp}, args.warmup, args.iters, args.calls).items()}
     result = dict(metric="center_point_targets_ms", unit="ms", value=ms["fused"]["median_ms"], warmup=args.warmup, iters=args.iters, calls_per_window=args.calls,
                   shape=dict(B=args.batch, N=int(boxes.shape[1]), D=9, T=len(TASKS), grid=list(CFG["grid_size"])),
                   objects=int(sizes.sum()), kept=int(ref[6].sum()), fused=ms["fused"], torch=ms["torch"],
                   speedup_median=round(ms["torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
-                  launches_fused=n_fused if n_fused is not None else "not measured",
-                  launches_torch=n_torch if n_torch is not None else "not measured",
+                  launches_fused=shown(launches(fused)), launches_torch=shown(launches(comp)),
                   integer_mismatches_vs_torch=mismatch, targets_max_abs_diff_vs_torch=terr)
     lines = [f"center_point_targets  B={args.batch} N<={boxes.shape[1]} D=9 T={len(TASKS)} grid 180x180: {int(sizes.sum())} objects, "
              f"{int(ref[6].sum())} kept",
@@ -184,10 +130,7 @@ def main():
              f"  torch   median {ms['torch']['median_ms']:.4f} ms  min {ms['torch']['min_ms']:.4f} ms  launches {result['launches_torch']}",
              f"  integer outputs that differ from the torch composition: {mismatch}; targets max abs diff {terr:.3e}",
              json.dumps(result)]
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -23,20 +23,11 @@ Prints a few lines of log per shape and ONE JSON line.
 
     python3 scripts/bench_depth_targets.py [--warmup 10] [--blocks 3] [--iters 40] [--calls 20] [--baseline-calls 2] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "examples"), os.path.join(ROOT, "scripts")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
-
-from bench_image_prep import launches, timed_windows  # noqa: E402
+from measure import block_summary, emit, gpu, launches, parser, shown, timed_windows
 
 SOURCE_HW, OUTPUT_HW, CAMERAS = (900, 1600), (256, 704), 6
 SHAPES = ((8, 34000), (8, 250000), (1, 34000), (1, 250000))
@@ -45,19 +36,13 @@ TORCH = "torch composition"
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=10)
+    ap = parser(warmup=10, iters=40, calls=20)
     ap.add_argument("--blocks", type=int, default=3, help="blocks per row; the rows take turns inside a block")
-    ap.add_argument("--iters", type=int, default=40, help="timed windows per block")
-    ap.add_argument("--calls", type=int, default=20, help="back-to-back library calls per window")
     ap.add_argument("--baseline-calls", type=int, default=2, help="back-to-back torch-composition calls per window")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_depth_targets.py measures on a GPU; none is visible")
+    dev = gpu()
     from depth_targets_step import STRIDE, composed_targets, fused_targets, image_matrices, make_scene
 
-    dev = torch.device("cuda", 0)
     h, w = -(-OUTPUT_HW[0] // STRIDE), -(-OUTPUT_HW[1] // STRIDE)
     lines, results = [], []
     for B, P in SHAPES:
@@ -84,13 +69,8 @@ def main():
             for r in rows:
                 n = args.baseline_calls if r == TORCH else args.calls
                 blocks[r].append(timed_windows(calls[r], 3 if r == TORCH else args.warmup, args.iters, n))
-        n_launch = {r: launches(calls[r]) for r in rows}
-        n_launch = {r: v if v is not None else "not measured" for r, v in n_launch.items()}
-        ms = {r: dict(block_medians_ms=[b["median_ms"] for b in blocks[r]],
-                      median_ms=round(statistics.median(b["median_ms"] for b in blocks[r]), 5),
-                      min_ms=round(min(b["min_ms"] for b in blocks[r]), 5),
-                      spread_ms=round(max(b["median_ms"] for b in blocks[r]) - min(b["median_ms"] for b in blocks[r]), 5),
-                      timed_s=round(sum(b["timed_s"] for b in blocks[r]), 3)) for r in rows}
+        n_launch = {r: shown(launches(calls[r])) for r in rows}
+        ms = {r: block_summary(blocks[r]) for r in rows}
         rule_rows = -(-h // max(1, min(h, 64 // (B * CAMERAS))))       # the library's rule, restated
         workgroups = {"fused": B * CAMERAS * -(-h // rule_rows), TORCH: None}
         workgroups.update({f"fused, bands of {r} rows": B * CAMERAS * -(-h // r) for r in BAND_ROWS})
@@ -139,10 +119,7 @@ def main():
                   blocks=args.blocks, iters=args.iters, calls_per_window=args.calls, baseline_calls_per_window=args.baseline_calls,
                   sizes=results)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

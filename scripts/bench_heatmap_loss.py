@@ -10,18 +10,12 @@ is larger than the 256 MB Infinity Cache, so back-to-back iterations read from H
 
     python3 scripts/bench_heatmap_loss.py [--warmup 20] [--iters 200] [--out FILE]
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import call_times, emit, gpu, parser   # puts the repository root on the path
 
 import bench_workloads as wl  # noqa: E402
 
@@ -39,32 +33,13 @@ def composition(logits, target, alpha=2.0, gamma=4.0, clamp_eps=1e-4):
     return (pos_loss + neg_loss).sum() / num_pos
 
 
-def median_ms(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in pairs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    return statistics.median(a.elapsed_time(b) for a, b in pairs)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    args = ap.parse_args()
+    args = parser(warmup=20, iters=200).parse_args()
 
     from accvlab.batching_helpers import combine_data
     from accvlab.draw_heatmap import draw_heatmap_batched, gaussian_focal_loss
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_heatmap_loss.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", 0)
+    dev = gpu()
     centers_l, radii_l = wl.heatmap_objects(B, H, W, 1, 128, "A", seed=42)
     centers = combine_data(centers_l, device=dev)
     radii = combine_data(radii_l, device=dev, other_with_same_sample_sizes=centers)
@@ -100,10 +75,9 @@ def main():
         with torch.no_grad():
             fl = float(gaussian_focal_loss(x, target))
             cl = float(composition(x, target))
-        ms = {k: median_ms(f, args.warmup, args.iters)
+        ms = {k: round(statistics.median(call_times({k: f}, args.warmup, args.iters)[k]), 4)      # one after the other, not in turns
               for k, f in (("fused_fwd_ms", fused_fwd), ("fused_fwd_bwd_ms", fused_fwd_bwd), ("torch_fwd_ms", comp_fwd),
                            ("torch_fwd_bwd_ms", comp_fwd_bwd))}
-        ms = {k: round(v, 4) for k, v in ms.items()}
         result[name] = dict(
             ms,
             fwd_bytes=fwd_bytes,
@@ -117,11 +91,7 @@ def main():
         )
         del x
     result["value"] = result["f32"]["fused_fwd_bwd_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

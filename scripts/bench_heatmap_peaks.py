@@ -10,19 +10,13 @@ device-event-timed iterations of accvlab.draw_heatmap.heatmap_peaks and of the c
 
     python3 scripts/bench_heatmap_peaks.py [--warmup 10] [--iters 50] [--out FILE]
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
+import torch.nn.functional as F
 
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+from measure import call_times, emit, gpu, parser
 
 HBM_BPS = 8.0e12
 CASES = [
@@ -46,31 +40,12 @@ def composition(heat, k, kernel=3, per_class=False):
     return scores, inds, clses, ys, xs
 
 
-def median_ms(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in pairs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    return statistics.median(a.elapsed_time(b) for a, b in pairs)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    args = ap.parse_args()
+    args = parser(warmup=10, iters=50).parse_args()
 
     from accvlab.draw_heatmap import heatmap_peaks
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_heatmap_peaks.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", 0)
+    dev = gpu()
     result = {"metric": "heatmap_peaks_ms", "unit": "ms", "kernel": 3, "warmup": args.warmup, "iters": args.iters,
               "hbm_peak_tbps": 8.0, "cases": {}}
     for name, shape, dtype, k, per_class in CASES:
@@ -82,8 +57,8 @@ def main():
         comp = composition(heat, k, per_class=per_class)
         # torch.topk orders equal scores arbitrarily: compare the scores, which are equal as multisets in sorted order
         scores_equal = torch.equal(fused.scores.reshape(-1, k).float(), comp[0].reshape(-1, k).float())
-        ms_fused = median_ms(lambda: heatmap_peaks(x, k, per_class=per_class), args.warmup, args.iters)
-        ms_torch = median_ms(lambda: composition(heat, k, per_class=per_class), args.warmup, args.iters)
+        ms_fused, ms_torch = (statistics.median(call_times({"f": f}, args.warmup, args.iters)["f"])     # one after the other
+                              for f in (lambda: heatmap_peaks(x, k, per_class=per_class), lambda: composition(heat, k, per_class=per_class)))
         nbytes = heat.numel() * heat.element_size()
         entry = {"shape": list(shape), "dtype": str(dtype).replace("torch.", ""), "k": k, "per_class": per_class,
                  "map_bytes": nbytes, "in_infinity_cache": nbytes < 256 * 2 ** 20, "fused_ms": round(ms_fused, 4),
@@ -93,11 +68,7 @@ def main():
         result["cases"][name] = entry
         del heat, x, fused, comp
     result["value"] = result["cases"][CASES[0][0]]["fused_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

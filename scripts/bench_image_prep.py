@@ -28,18 +28,11 @@ Prints a few lines of log per shape and ONE JSON line.
 
     python3 scripts/bench_image_prep.py [--warmup 10] [--iters 100] [--calls 50] [--baseline-calls 2] [--probe] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "examples")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, shown, timed_windows
 
 SOURCE_HW = (900, 1600)
 SHAPES = (("warp", 8, 6, (256, 704)), ("no_warp", 8, 6, None))
@@ -66,39 +59,6 @@ def sampled_source_bytes(transform, source_hw, output_hw):
             ok = (x >= 0) & (x < Ws) & (y >= 0) & (y < Hs)
             touched[y[ok], x[ok]] = True
     return 3 * int(touched.sum())
-
-
-def timed_windows(f, warmup, iters, calls):
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    events = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            f()
-        b.record()
-        events.append((a, b))
-        torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) / calls for a, b in events]
-    return dict(median_ms=round(statistics.median(ms), 5), min_ms=round(min(ms), 5), timed_s=round(sum(ms) * calls / 1e3, 3))
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        return len([e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                    and not e.name.lower().startswith(("memcpy", "memset"))])
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
 
 
 def probe_warp_shape(dev, args):
@@ -129,21 +89,15 @@ def probe_warp_shape(dev, args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--iters", type=int, default=100, help="timed windows per side")
-    ap.add_argument("--calls", type=int, default=50, help="back-to-back fused calls per window")
+    ap = parser(warmup=10, iters=100, calls=50)
     ap.add_argument("--probe", action="store_true", help="also time the warp shape with one cost taken away at a time")
     ap.add_argument("--baseline-calls", type=int, default=2, help="back-to-back torch-composition calls per window")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_image_prep.py measures on a GPU; none is visible")
+    dev = gpu()
     from image_prep_step import MEAN, STD, step_parameters, torch_composition
 
     from accvlab.image_prep import padded_hw, prepare_images
 
-    dev = torch.device("cuda", 0)
     lines, results = [], []
     for name, samples, cameras, output_hw in SHAPES:
         B = samples * cameras
@@ -176,10 +130,8 @@ def main():
         diff = float((got - ref).abs().max())
         differ = int(not diff <= bar)
         del ref
-        ms = dict(fused=timed_windows(fused, args.warmup, args.iters, args.calls),
-                  torch=timed_windows(composed, 3, args.iters, args.baseline_calls))
-        n = {k: launches(f) for k, f in (("fused", fused), ("torch", composed))}
-        n = {k: v if v is not None else "not measured" for k, v in n.items()}
+        ms = dict(fused=timed_windows(fused, args.warmup, args.iters, args.calls), torch=timed_windows(composed, 3, args.iters, args.baseline_calls))
+        n = {k: shown(launches(f)) for k, f in (("fused", fused), ("torch", composed))}
         out_bytes = out.numel() * out.element_size()
         rate = (source_bytes + out_bytes) / (ms["fused"]["median_ms"] * 1e-3)
         res = dict(shape=dict(name=name, B=B, source_h=SOURCE_HW[0], source_w=SOURCE_HW[1], output_h=Ho, output_w=Wo, padded_h=Hp,
@@ -207,10 +159,7 @@ def main():
     result = dict(metric="prepare_images_ms", unit="ms", value=results[0]["fused"]["median_ms"], warmup=args.warmup, iters=args.iters,
                   calls_per_window=args.calls, baseline_calls_per_window=args.baseline_calls, kernel_paths=["gather"], sizes=results, probe=probe)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -16,21 +16,13 @@ Plus F3 forward + backward (run_batched vs run_batched_on_device, fused and comp
 
     python3 scripts/bench_linear_assignment.py [--warmup 5] [--iters 30] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "examples")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import numpy as np
+import torch
+from scipy.optimize import linear_sum_assignment
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-from scipy.optimize import linear_sum_assignment  # noqa: E402
+from measure import call_times, emit, gpu, parser, summary, wall_times
 
 CASES = [
     # name, batch, queries, max_gt, min_gt
@@ -87,47 +79,17 @@ def dijkstra_steps(cost):
     return steps
 
 
-def wall(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4)}
-
-
-def device(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in pairs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    ts = [a.elapsed_time(b) for a, b in pairs]
-    return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_linear_assignment.py measures on a GPU; none is visible")
+    args = parser(warmup=5, iters=30).parse_args()
+    dev = gpu()
 
     import matched_loss as ml
 
     import accvlab.batching_helpers as bh
 
-    dev = torch.device("cuda", 0)
+    stats = lambda ms: {k: v for k, v in summary(ms, digits=4).items() if k != "timed_s"}    # noqa: E731 - median and minimum
+    wall = lambda fn: stats(wall_times(fn, args.iters, args.warmup))                          # noqa: E731
+    device = lambda fn: stats(call_times({"fn": fn}, args.warmup, args.iters)["fn"])          # noqa: E731
     result = {"metric": "linear_assignment_ms", "unit": "ms", "warmup": args.warmup, "iters": args.iters, "cases": {}}
 
     def roundtrip(cost):
@@ -161,12 +123,11 @@ def main():
 
         entry = {"B": B, "queries": Q, "max_gt": G, "min_gt": G0, "gt_sizes": cost.sample_sizes.tolist(),
                  "indices_equal_scipy": same, "steps_per_frame": steps}
-        entry["roundtrip"] = wall(lambda: roundtrip(cost), args.warmup, args.iters)
-        entry["op_check"] = wall(lambda: bh.batched_linear_sum_assignment(cost), args.warmup, args.iters)
-        entry["op_nocheck"] = wall(lambda: bh.batched_linear_sum_assignment(cost, check=False), args.warmup, args.iters)
+        entry["roundtrip"] = wall(lambda: roundtrip(cost))
+        entry["op_check"] = wall(lambda: bh.batched_linear_sum_assignment(cost))
+        entry["op_nocheck"] = wall(lambda: bh.batched_linear_sum_assignment(cost, check=False))
         for t in (64, 256, 1024):
-            entry[f"op_kernel_t{t}"] = device(lambda: bh.batched_linear_sum_assignment(cost, check=False, _threads=t),
-                                              args.warmup, args.iters)
+            entry[f"op_kernel_t{t}"] = device(lambda: bh.batched_linear_sum_assignment(cost, check=False, _threads=t))
         best = min(entry[f"op_kernel_t{t}"]["median_ms"] for t in (64, 256, 1024))
         entry["us_per_step_longest_frame_t256"] = round(entry["op_kernel_t256"]["median_ms"] * 1e3 / max(max(steps), 1), 3)
         entry["speedup_check_vs_roundtrip"] = round(entry["roundtrip"]["median_ms"] / entry["op_check"]["median_ms"], 2)
@@ -178,17 +139,12 @@ def main():
                     p = [t.clone().requires_grad_(True) for t in inp[3:]]
                     run(*inp[:3], *p, fused=fused).sum().backward()
                 tag = "fused" if fused else "composed"
-                entry[f"f3_fwd_bwd_{tag}_scipy"] = wall(lambda: step(ml.run_batched), args.warmup, args.iters)
-                entry[f"f3_fwd_bwd_{tag}_on_device"] = wall(lambda: step(ml.run_batched_on_device), args.warmup,
-                                                            args.iters)
+                entry[f"f3_fwd_bwd_{tag}_scipy"] = wall(lambda: step(ml.run_batched))
+                entry[f"f3_fwd_bwd_{tag}_on_device"] = wall(lambda: step(ml.run_batched_on_device))
         result["cases"][name] = entry
     f3 = result["cases"][CASES[0][0]]
     result["value"] = f3["op_check"]["median_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

@@ -12,18 +12,12 @@ line.
 
     python3 scripts/bench_matched_focal_loss.py [--warmup 20] [--iters 100] [--out FILE] [--cases a_f32,d_bf16]
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "examples")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import call_times, emit, gpu, parser   # puts tests/ and examples/ on the path
 
 import matched_focal_loss_cases as mf  # noqa: E402
 import matched_loss as ml  # noqa: E402
@@ -31,24 +25,6 @@ import matched_loss as ml  # noqa: E402
 SHAPES = {"a": (8, 900, 10, 100), "b": (16, 300, 91, 40), "c": (48, 900, 80, 60), "d": (32, 8400, 80, 60)}
 CASES = {f"{k}_{n}": dict(shape=v, dtype=d) for k, v in SHAPES.items() for n, d in (("f32", torch.float32), ("bf16", torch.bfloat16))}
 COPY_CEILING_TBPS = 6.29   # float4 copy, DESIGN.md §9b
-
-
-def timed(fns, warmup, iters):
-    """medians in ms of the callables, run one after the other inside every iteration"""
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    events = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            events[k].append((a, b))
-    torch.cuda.synchronize()
-    return {k: round(statistics.median(a.elapsed_time(b) for a, b in v), 4) for k, v in events.items()}
 
 
 def make(cfg, dev):
@@ -75,8 +51,9 @@ def run_case(cfg, dev, warmup, iters):
 
     with torch.no_grad():
         lf, lc = float(fused().sum()), float(comp().sum())
-    ms = timed({"fused_fwd_ms": fwd(fused), "torch_fwd_ms": fwd(comp), "fused_fwd_bwd_ms": fwd_bwd(fused),
-                "torch_fwd_bwd_ms": fwd_bwd(comp)}, warmup, iters)
+    ms = call_times({"fused_fwd_ms": fwd(fused), "torch_fwd_ms": fwd(comp), "fused_fwd_bwd_ms": fwd_bwd(fused),
+                     "torch_fwd_bwd_ms": fwd_bwd(comp)}, warmup, iters)
+    ms = {k: round(statistics.median(v), 4) for k, v in ms.items()}
     nbytes = x.numel() * x.element_size()
     fused_bwd = max(ms["fused_fwd_bwd_ms"] - ms["fused_fwd_ms"], 1e-6)
     return dict(ms, shape=list(x.shape), dtype=str(x.dtype).split(".")[-1], pairs=pairs, logit_bytes=nbytes,
@@ -111,31 +88,22 @@ def trace_case(cfg, dev, iters, count):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=100)
+    ap = parser(warmup=20, iters=100)
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--trace", type=int, default=0, help="run this many plain iterations per case instead of timing")
     ap.add_argument("--launch-count", action="store_true", help="count the launches of both with torch's profiler instead")
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_matched_focal_loss.py measures on a GPU; none is visible")
+    dev = gpu()
     plain = args.trace or args.launch_count
     if args.iters < 100 and not plain:
         raise SystemExit("medians of at least 100 iterations are reported")
-    dev = torch.device("cuda", 0)
     result = {"metric": "matched_focal_loss_fwd_bwd_ms", "unit": "ms", "warmup": args.warmup, "iters": args.iters}
     for name in args.cases.split(","):
         result[name] = (trace_case(CASES[name], dev, args.trace, args.launch_count) if plain
                         else run_case(CASES[name], dev, args.warmup, args.iters))
     if not plain:
         result["value"] = result[args.cases.split(",")[0]]["fused_fwd_bwd_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

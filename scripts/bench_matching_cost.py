@@ -14,19 +14,11 @@ the composed cost + on-device solver + fused loss (examples/matched_loss.run_bat
 
     python3 scripts/bench_matching_cost.py [--warmup 10] [--iters 50] [--out FILE] [--op-only]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "examples")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import call_times, emit, gpu, parser, summary, wall_times
 
 CASES = [
     # name, batch, queries, classes, max_gt
@@ -35,33 +27,6 @@ CASES = [
     ("streampetr", 8, 900, 10, 150),
     ("large", 64, 900, 10, 300),
 ]
-
-
-def wall(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5)}
-
-
-def device(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in pairs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    ts = [a.elapsed_time(b) for a, b in pairs]
-    return {"median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5)}
 
 
 def xyxy(b):
@@ -123,36 +88,34 @@ def make(name, B, Q, C, G, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap = parser(warmup=10, iters=50)
     ap.add_argument("--op-only", action="store_true")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_matching_cost.py measures on a GPU; none is visible")
+    dev = gpu()
 
     import matched_loss as ml
 
     import accvlab.batching_helpers as bh
 
-    dev = torch.device("cuda", 0)
+    stats = lambda ms: {k: v for k, v in summary(ms).items() if k != "timed_s"}               # noqa: E731 - median and minimum
+    wall = lambda fn: stats(wall_times(fn, args.iters, args.warmup))                          # noqa: E731
+    device = lambda fn: stats(call_times({"fn": fn}, args.warmup, args.iters)["fn"])          # noqa: E731
     result = {"metric": "matching_cost_ms", "unit": "ms", "warmup": args.warmup, "iters": args.iters, "cases": {}}
     for name, B, Q, C, G in CASES:
         inp, torch_cost, kw = make(name, B, Q, C, G, dev)
         op = lambda: bh.batched_matching_cost(*inp, **kw)
         if args.op_only:
-            wall(op, args.warmup, args.iters)
+            wall(op)
             continue
         got = op()
         want = torch_cost()
         mask = got.mask.unsqueeze(1).expand_as(want)
         entry = {"B": B, "queries": Q, "classes": C, "max_gt": G, "gt_sizes": got.sample_sizes.tolist(),
                  "max_abs_diff_vs_torch": float((got.tensor - want)[mask].abs().max()) if mask.any() else 0.0}
-        entry["torch"] = wall(torch_cost, args.warmup, args.iters)
-        entry["op"] = wall(op, args.warmup, args.iters)
-        entry["torch_kernel"] = device(torch_cost, args.warmup, args.iters)
-        entry["op_kernel"] = device(op, args.warmup, args.iters)
+        entry["torch"] = wall(torch_cost)
+        entry["op"] = wall(op)
+        entry["torch_kernel"] = device(torch_cost)
+        entry["op_kernel"] = device(op)
         entry["speedup_wall"] = round(entry["torch"]["median_ms"] / entry["op"]["median_ms"], 2)
         entry["speedup_device"] = round(entry["torch_kernel"]["median_ms"] / entry["op_kernel"]["median_ms"], 2)
         result["cases"][name] = entry
@@ -162,16 +125,12 @@ def main():
                 def step(run=run):
                     p = [t.clone().requires_grad_(True) for t in inp_f3[3:]]
                     run(*inp_f3[:3], *p, fused=True).sum().backward()
-                entry[f"f3_fwd_bwd_{tag}_on_device_fused_loss"] = wall(step, args.warmup, args.iters)
+                entry[f"f3_fwd_bwd_{tag}_on_device_fused_loss"] = wall(step)
     if args.op_only:
         print(json.dumps({"op_only": True}))
         return
     result["value"] = result["cases"]["f3"]["op"]["median_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

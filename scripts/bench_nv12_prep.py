@@ -24,20 +24,11 @@ Prints a few lines of log per shape and ONE JSON line.
 
     python3 scripts/bench_nv12_prep.py [--warmup 10] [--blocks 3] [--iters 40] [--calls 20] [--baseline-calls 2] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "examples"), os.path.join(ROOT, "scripts")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
-
-from bench_image_prep import launches, timed_windows  # noqa: E402
+from measure import block_summary, emit, gpu, launches, parser, shown, timed_windows
 
 SOURCE_HW = (900, 1600)
 PITCH = 1664
@@ -86,22 +77,16 @@ def sampled_counts(transforms, source_hw, output_hw, B):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=10)
+    ap = parser(warmup=10, iters=40, calls=20)
     ap.add_argument("--blocks", type=int, default=3, help="blocks per row; the rows take turns inside a block")
-    ap.add_argument("--iters", type=int, default=40, help="timed windows per block")
-    ap.add_argument("--calls", type=int, default=20, help="back-to-back library calls per window")
     ap.add_argument("--baseline-calls", type=int, default=2, help="back-to-back torch-composition calls per window")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_nv12_prep.py measures on a GPU; none is visible")
+    dev = gpu()
     from image_prep_step import MEAN, STD, step_parameters
     from nv12_prep_step import random_surfaces, torch_nv12_to_rgb
 
     from accvlab.image_prep import nv12_planes, nv12_to_rgb, padded_hw, prepare_images, prepare_images_nv12
 
-    dev = torch.device("cuda", 0)
     Hs, Ws = SOURCE_HW
     lines, results = [], []
     for name, samples, cameras, output_hw in SHAPES:
@@ -135,13 +120,8 @@ def main():
                 n = args.baseline_calls if r.startswith("torch") else args.calls
                 blocks[r].append(timed_windows(calls[r], 3 if r.startswith("torch") else args.warmup, args.iters, n))
         calls["nv12_to_rgb"]()      # the torch row does not write rgb; keep it the conversion's for the profiler pass
-        n_launch = {r: launches(calls[r]) for r in ROWS}
-        n_launch = {r: v if v is not None else "not measured" for r, v in n_launch.items()}
-        ms = {r: dict(block_medians_ms=[b["median_ms"] for b in blocks[r]],
-                      median_ms=round(statistics.median(b["median_ms"] for b in blocks[r]), 5),
-                      min_ms=round(min(b["min_ms"] for b in blocks[r]), 5),
-                      spread_ms=round(max(b["median_ms"] for b in blocks[r]) - min(b["median_ms"] for b in blocks[r]), 5),
-                      timed_s=round(sum(b["timed_s"] for b in blocks[r]), 3)) for r in ROWS}
+        n_launch = {r: shown(launches(calls[r])) for r in ROWS}
+        ms = {r: block_summary(blocks[r]) for r in ROWS}
         out_bytes = out.numel() * out.element_size()
         full_planes = B * (Hs * Ws + 2 * ((Hs + 1) // 2) * ((Ws + 1) // 2))
         moved = {"fused": luma + 2 * chroma + out_bytes,
@@ -177,10 +157,7 @@ def main():
                   blocks=args.blocks, iters=args.iters, calls_per_window=args.calls, baseline_calls_per_window=args.baseline_calls,
                   sizes=results)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

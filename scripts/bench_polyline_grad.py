@@ -12,18 +12,12 @@ that both backward inputs are used.  Prints ONE JSON line (``--out`` also writes
 
 ``--only-ours`` skips the composition (the kernel trace in profiles/ was taken that way, with few iterations).
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
+from measure import call_times, emit, gpu, parser
 
 SHAPES = [("config3_lanes", 256, 24, 256), ("b64_p100_q100", 64, 100, 100), ("b64_p5000_q5000", 64, 5000, 5000),
           ("b1_p5000_q5000", 1, 5000, 5000)]
@@ -53,32 +47,14 @@ def composition(points, fractions):
     return torch.where(interp.unsqueeze(-1), p0 + w1 * (p1 - p0), pj), total
 
 
-def median_ms(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in pairs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    return statistics.median(a.elapsed_time(b) for a, b in pairs)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap = parser(warmup=20, iters=200)
     ap.add_argument("--only-ours", action="store_true", help="time accvlab's operators only")
     args = ap.parse_args()
 
     from accvlab.lane_helpers.polyline import interpolate, lengths
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_polyline_grad.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", 0)
+    dev = gpu()
     result = {"metric": "polyline_interpolate_lengths_fwd_bwd_ms", "unit": "ms", "dtype": "float32", "dims": 2,
               "relative": True, "warmup": args.warmup, "iters": args.iters, "shapes": {}}
     for name, b, p, q in SHAPES:
@@ -105,17 +81,13 @@ def main():
         runs = [("ours_fwd_ms", ours_fwd), ("ours_fwd_bwd_ms", ours_fwd_bwd)]
         if not args.only_ours:
             runs.append(("torch_fwd_bwd_ms", comp_fwd_bwd))
-        ms = {k: round(median_ms(fn, args.warmup, args.iters), 4) for k, fn in runs}
+        ms = {k: round(statistics.median(call_times({k: fn}, args.warmup, args.iters)[k]), 4) for k, fn in runs}   # one after the other
         entry = dict(ms, batch=b, points=p, queries=q)
         if not args.only_ours:
             entry["speedup_fwd_bwd"] = round(ms["torch_fwd_bwd_ms"] / ms["ours_fwd_bwd_ms"], 2)
         result["shapes"][name] = entry
     result["value"] = result["shapes"]["config3_lanes"]["ours_fwd_bwd_ms"]
-    line = json.dumps(result)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    emit([json.dumps(result)], args.out)
 
 
 if __name__ == "__main__":

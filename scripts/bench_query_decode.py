@@ -24,19 +24,11 @@ reports during one call; "not measured" if either is unavailable.  Prints a few 
 
     python3 scripts/bench_query_decode.py [--warmup 20] [--iters 10] [--calls 10] [--out FILE]
 """
-import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.dirname(os.path.abspath(__file__))):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
-
-from bench_box_decode import launches, round_trips, timed  # noqa: E402
+from measure import emit, gpu, launches, parser, round_trips, shown, summary, window_times
 
 BATCHES = (1, 8)
 SHAPES = ((900, 10, 300), (900, 80, 300), (300, 80, 100))
@@ -102,18 +94,10 @@ def peaks_route(cls, rows, K, heatmap_peaks):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=10, help="timed blocks per side")
-    ap.add_argument("--calls", type=int, default=10, help="back-to-back calls per block")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_query_decode.py measures on a GPU; none is visible")
+    args = parser(warmup=20, iters=10, calls=10).parse_args()
+    dev = gpu()
     from accvlab.draw_heatmap import heatmap_peaks, query_box_decode_3d
 
-    dev = torch.device("cuda", 0)
-    show = lambda n: n if n is not None else "not measured"   # noqa: E731
     lines, results = [], []
     for Q, C, K in SHAPES:
         for B in BATCHES:
@@ -129,29 +113,26 @@ def main():
             worst = max(float((mine[0] - ref[0]).abs().max()), float((mine[1] - ref[1]).abs().max()))
             dets = int(got.boxes.sample_sizes.sum())
             sides = {"fused": fused, "torch": comp, "peaks_torch": prev}
-            ms = timed(sides, args.warmup, args.iters, args.calls)
+            ms = {k: summary(v, args.calls, with_max=True) for k, v in window_times(sides, args.warmup, args.iters, args.calls).items()}
             n = {k: launches(f) for k, f in sides.items()}
             r = {k: round_trips(f) for k, f in sides.items()}
             results.append(dict(B=B, Q=Q, C=C, max_num=K, detections=dets, **ms,
                                 speedup_median_vs_torch=round(ms["torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
                                 speedup_median_vs_peaks_torch=round(ms["peaks_torch"]["median_ms"] / ms["fused"]["median_ms"], 2),
-                                launches={k: show(v) for k, v in n.items()}, host_round_trips={k: show(v) for k, v in r.items()},
+                                launches={k: shown(v) for k, v in n.items()}, host_round_trips={k: shown(v) for k, v in r.items()},
                                 output_tensors_that_differ=len(differ), tensors_that_differ=differ, largest_difference=worst))
             lines += [f"query_box_decode_3d  B={B} Q={Q} C={C} max_num={K}: {dets} detections",
                       f"  {args.warmup} warm-up calls, {args.iters} blocks of {args.calls} calls per side, alternating; timed {ms['fused']['timed_s']} s "
                       f"fused, {ms['torch']['timed_s']} s torch, {ms['peaks_torch']['timed_s']} s peaks + torch"]
             for key, label in (("fused", "(a) fused        "), ("torch", "(b) torch        "), ("peaks_torch", "(c) peaks + torch")):
-                lines.append(f"  {label} median {ms[key]['median_ms']:.4f} ms  min {ms[key]['min_ms']:.4f} ms  launches {show(n[key])}  "
-                             f"host round trips {show(r[key])}")
+                lines.append(f"  {label} median {ms[key]['median_ms']:.4f} ms  min {ms[key]['min_ms']:.4f} ms  launches {shown(n[key])}  "
+                             f"host round trips {shown(r[key])}")
             lines.append(f"  against the torch composition: {len(differ)} of 5 output tensors differ ({', '.join(differ) or 'none'}; largest "
                          f"difference {worst:.3e})")
     result = dict(metric="query_box_decode_3d_ms", unit="ms", value=results[0]["fused"]["median_ms"], warmup=args.warmup, iters=args.iters,
                   calls_per_block=args.calls, runs=results)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

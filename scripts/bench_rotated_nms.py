@@ -22,40 +22,29 @@ line.
 
     python3 scripts/bench_rotated_nms.py [--warmup 20] [--iters 10] [--calls 20] [--out profiles/rotated_nms_bench.log]
 """
-import argparse
 import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # the workload below is a sibling's
 import torch  # noqa: E402
 
-from bench_center_decode import CFG, OPTS, TASKS, launches, make_inputs, timed  # noqa: E402
+from bench_center_decode import CFG, OPTS, TASKS, make_inputs  # noqa: E402
+from measure import emit, gpu, launches, parser, shown, summary, window_times  # noqa: E402
 
 IOU_THRESHOLD = 0.2
 POST_MAX_SIZE = 83
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=10, help="timed blocks per side")
-    ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per block")
+    ap = parser(warmup=20, iters=10, calls=20)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--k", type=int, default=500)
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_rotated_nms.py measures on a GPU; none is visible")
+    dev = gpu()
     from accvlab.batching_helpers import RaggedBatch
     from accvlab.draw_heatmap import CenterPointDetections, center_point_decode, heatmap_peaks, rotated_nms_bev
 
-    dev = torch.device("cuda", 0)
     logits, heads = make_inputs(args.batch, dev)
     K = args.k
     opts = dict(OPTS, nms_threshold=None, post_max_size=None)
@@ -91,29 +80,26 @@ def main():
     for d, r in zip(got, ref):
         mismatch += int(not torch.equal(d.boxes.sample_sizes, r.boxes.sample_sizes))
         mismatch += sum(int(not torch.equal(x.tensor.view(torch.uint8), y.tensor.view(torch.uint8))) for x, y in zip(d, r))
-    ms = timed({"nms": nms_only, "fused": fused, "round_trip": round_trip}, args.warmup, args.iters, args.calls)
+    ms = window_times({"nms": nms_only, "fused": fused, "round_trip": round_trip}, args.warmup, args.iters, args.calls)
+    ms = {k: summary(v, args.calls, with_max=True) for k, v in ms.items()}
     n_nms, n_fused, n_trip = launches(nms_only), launches(fused), launches(round_trip)
-    show = lambda n: n if n is not None else "not measured"   # noqa: E731
     T = len(TASKS)
     result = dict(metric="rotated_nms_bev_ms", unit="ms", value=ms["nms"]["median_ms"], warmup=args.warmup, iters=args.iters,
                   calls_per_block=args.calls, shape=dict(B=args.batch, T=T, N=K, iou_threshold=IOU_THRESHOLD, post_max_size=POST_MAX_SIZE),
                   decoded=decoded, kept=kept, nms=ms["nms"], fused=ms["fused"], round_trip=ms["round_trip"],
                   speedup_median_nms_vs_round_trip=round(ms["round_trip"]["median_ms"] / ms["nms"]["median_ms"], 2),
-                  launches_nms=show(n_nms), launches_fused=show(n_fused), launches_round_trip=show(n_trip),
+                  launches_nms=shown(n_nms), launches_fused=shown(n_fused), launches_round_trip=shown(n_trip),
                   host_round_trips=T, host_copies_round_trip=10 * T, tensors_that_differ_from_the_round_trip=mismatch)
     lines = [f"rotated_nms_bev  B={args.batch} T={T} N={K} iou_threshold={IOU_THRESHOLD} post_max_size={POST_MAX_SIZE}: {decoded} decoded, {kept} kept"
              f" on {torch.cuda.get_device_name(0)}",
              f"  {args.warmup} warm-up calls, {args.iters} blocks of {args.calls} calls per side, alternating",
-             f"  nms alone           median {ms['nms']['median_ms']:.4f} ms  min {ms['nms']['min_ms']:.4f} ms  max {ms['nms']['max_ms']:.4f} ms  launches {show(n_nms)}  host round trips 0",
-             f"  peaks+decode+nms    median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {show(n_fused)}  host round trips 0",
-             f"  D2H, host nms, H2D  median {ms['round_trip']['median_ms']:.4f} ms  min {ms['round_trip']['min_ms']:.4f} ms  launches {show(n_trip)}  "
+             f"  nms alone           median {ms['nms']['median_ms']:.4f} ms  min {ms['nms']['min_ms']:.4f} ms  max {ms['nms']['max_ms']:.4f} ms  launches {shown(n_nms)}  host round trips 0",
+             f"  peaks+decode+nms    median {ms['fused']['median_ms']:.4f} ms  min {ms['fused']['min_ms']:.4f} ms  launches {shown(n_fused)}  host round trips 0",
+             f"  D2H, host nms, H2D  median {ms['round_trip']['median_ms']:.4f} ms  min {ms['round_trip']['min_ms']:.4f} ms  launches {shown(n_trip)}  "
              f"host round trips {T} (one per task: 5 copies down, each waiting for the device, and 5 up)",
              f"  against the round trip: {mismatch} output tensors differ",
              json.dumps(result)]
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -21,20 +21,12 @@ Prints a few lines of log per size and ONE JSON line.
 
     python3 scripts/bench_visible_bboxes.py [--warmup 20] [--iters 100] [--calls 20] [--baseline-iters 3] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from measure import emit, gpu, launches, parser, shown, summary, timed_windows, wall_times
 
 SIZES = ((48, 900, 1600, 64), (64, 1080, 1920, 128))
 MIN_SIZE = 2.0
@@ -106,65 +98,14 @@ def torch_painter(boxes, depths, sizes, H, W):
     return out & big & live
 
 
-def timed_windows(f, warmup, iters, calls):
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    events = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            f()
-        b.record()
-        events.append((a, b))
-        torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) / calls for a, b in events]
-    return dict(median_ms=round(statistics.median(ms), 5), min_ms=round(min(ms), 5), timed_s=round(sum(ms) * calls / 1e3, 3))
-
-
-def timed_calls(f, iters):
-    f()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        t = time.perf_counter()
-        f()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t) * 1e3)
-    return dict(median_ms=round(statistics.median(ms), 3), min_ms=round(min(ms), 3), timed_s=round(sum(ms) / 1e3, 3))
-
-
-def launches(f):
-    """kernels on the device in one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        return len([e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
-                    and not e.name.lower().startswith(("memcpy", "memset"))])
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=100, help="timed windows of the fused side")
-    ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per window")
+    ap = parser(warmup=20, iters=100, calls=20)
     ap.add_argument("--baseline-iters", type=int, default=3, help="timed calls of each baseline")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_visible_bboxes.py measures on a GPU; none is visible")
+    dev = gpu()
     from accvlab.batching_helpers import RaggedBatch
     from accvlab.draw_heatmap import visible_bbox_mask
 
-    dev = torch.device("cuda", 0)
     lines, results = [], []
     for B, H, W, n_max in SIZES:
         boxes, depths, sizes = make_inputs(B, H, W, n_max, dev)
@@ -178,9 +119,9 @@ def main():
         differ = dict(numpy=int(not torch.equal(got, ref_np)), torch=int(not torch.equal(got, ref_t)))
         elements = dict(numpy=int((got != ref_np).sum()), torch=int((got != ref_t).sum()))
         ms = dict(fused=timed_windows(fused, args.warmup, args.iters, args.calls),
-                  numpy=timed_calls(via_numpy, args.baseline_iters), torch=timed_calls(via_torch, args.baseline_iters))
-        n = {k: launches(f) for k, f in (("fused", fused), ("torch", via_torch))}
-        n = {k: v if v is not None else "not measured" for k, v in n.items()}
+                  numpy=summary(wall_times(via_numpy, args.baseline_iters), digits=3),
+                  torch=summary(wall_times(via_torch, args.baseline_iters), digits=3))
+        n = {k: shown(launches(f)) for k, f in (("fused", fused), ("torch", via_torch))}
         n["numpy"] = 0                                            # copies only, by construction
         trips = dict(fused=0, numpy=2, torch=1 + B)
         res = dict(shape=dict(B=B, H=H, W=W, N=int(boxes.shape[1])), boxes=int(sizes.sum()), kept=int(got.sum()),
@@ -201,10 +142,7 @@ def main():
     result = dict(metric="visible_bbox_mask_ms", unit="ms", value=results[0]["fused"]["median_ms"], warmup=args.warmup,
                   iters=args.iters, calls_per_window=args.calls, baseline_iters=args.baseline_iters, sizes=results)
     lines.append(json.dumps(result))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out)
     if any(v for r in results for v in r["output_tensors_that_differ"].values()):
         raise SystemExit("the masks differ from a baseline")
 

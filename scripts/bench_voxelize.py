@@ -16,70 +16,36 @@ Every row is timed in `--blocks` blocks, the rows taking turns inside a block; a
 is the median of its windows.  A row's median is the median of its block medians, its spread their max - min.  The verdict per
 baseline: the fused median below the baseline's by more than the margin, the larger spread of the two rows (what the
 measurement cannot resolve).  Launch counts come from torch's profiler in a separate pass (memsets and copies are not
-counted); host round trips are counted from the code.  Before anything is timed the five fused outputs are compared with both
+counted; the host round trip launches none by construction and is not profiled); host round trips are counted from the code.  Before anything is timed the five fused outputs are compared with both
 baselines bit for bit (the number of output tensors that differ).  `count + number alone` is the device time of the fused
 call's two prefix-sum launches through the profiler (their share of the call), or "not measured".
 Prints a few lines of log per shape and ONE JSON line.
 
     python3 scripts/bench_voxelize.py [--warmup 5] [--blocks 3] [--iters 20] [--calls 10] [--baseline-calls 1] [--out FILE]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "accv-lab_amd"), os.path.join(ROOT, "examples"), os.path.join(ROOT, "scripts")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import torch
 
-import torch  # noqa: E402
-
-from bench_image_prep import launches, timed_windows  # noqa: E402
+from measure import block_summary, emit, gpu, kernel_times, launches, parser, shown, timed_windows
 
 SHAPES = ((8, 34000), (8, 250000), (1, 34000), (1, 250000))
 FUSED, HOST, TORCH = "fused", "host round trip", "torch composition"
 ROUND_TRIPS = {FUSED: 0, HOST: 2, TORCH: 1}
 
 
-def kernel_times(f):
-    """name -> device time in ms of every kernel of one call, or None when the profiler cannot tell"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-
-        f()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            f()
-            torch.cuda.synchronize()
-        out = {}
-        for e in prof.events():
-            if str(getattr(e, "device_type", "")).endswith("CUDA"):
-                out[e.name] = out.get(e.name, 0.0) + e.device_time / 1e3
-        return out
-    except Exception:   # pragma: no cover - profiler builds differ
-        return None
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = parser(warmup=5, iters=20, calls=10)
     ap.add_argument("--blocks", type=int, default=3, help="blocks per row; the rows take turns inside a block")
-    ap.add_argument("--iters", type=int, default=20, help="timed windows per block")
-    ap.add_argument("--calls", type=int, default=10, help="back-to-back library calls per window")
     ap.add_argument("--baseline-calls", type=int, default=1, help="back-to-back baseline calls per window")
     ap.add_argument("--baseline-iters", type=int, default=5, help="timed windows per block of a baseline row")
-    ap.add_argument("--out", default=None, help="also write the log to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_voxelize.py measures on a GPU; none is visible")
+    dev = gpu()
     from voxelize_step import PILLARS, VOXELS, composed_voxels, differing, host_round_trip, make_cloud
 
     from accvlab.draw_heatmap import sample_bev_augmentation
     from accvlab.point_cloud import voxelize_points
 
-    dev = torch.device("cuda", 0)
     lines, results = [], []
     for grid_name, cfg, channels in (("pillars", PILLARS, 4), ("voxels", VOXELS, 5)):
         for B, P in SHAPES:
@@ -101,15 +67,10 @@ def main():
                     base = r != FUSED
                     blocks[r].append(timed_windows(calls[r], 1 if base else args.warmup, args.baseline_iters if base else args.iters,
                                                    args.baseline_calls if base else args.calls))
-            n_launch = {r: launches(calls[r]) for r in names}
-            n_launch = {r: v if v is not None else "not measured" for r, v in n_launch.items()}
+            n_launch = {r: 0 if r == HOST else shown(launches(calls[r])) for r in names}      # the round trip: copies only, by construction
             times = kernel_times(calls[FUSED])
             number_ms = round(sum(v for k, v in times.items() if "voxelize_number" in k or "voxelize_count" in k), 5) if times else None
-            ms = {r: dict(block_medians_ms=[b["median_ms"] for b in blocks[r]],
-                          median_ms=round(statistics.median(b["median_ms"] for b in blocks[r]), 5),
-                          min_ms=round(min(b["min_ms"] for b in blocks[r]), 5),
-                          spread_ms=round(max(b["median_ms"] for b in blocks[r]) - min(b["median_ms"] for b in blocks[r]), 5),
-                          timed_s=round(sum(b["timed_s"] for b in blocks[r]), 3)) for r in names}
+            ms = {r: block_summary(blocks[r]) for r in names}
             verdicts = {}
             for r in (HOST, TORCH):
                 margin = max(ms[FUSED]["spread_ms"], ms[r]["spread_ms"])
@@ -140,15 +101,12 @@ def main():
             lines.append(f"  count + number alone (the prefix sum over the frame's points): "
                          f"{'not measured' if number_ms is None else f'{number_ms:.4f} ms'}; output tensors differing from the host round trip: "
                          f"{differ[HOST]} of 5; from the torch composition: {differ[TORCH]} of 5")
-            print("\n".join(lines[-8:]), flush=True)
+            emit(lines[-8:])
     result = dict(metric="voxelize_points_ms", unit="ms", value=results[0]["rows"][FUSED]["median_ms"], warmup=args.warmup, blocks=args.blocks,
                   iters=args.iters, calls_per_window=args.calls, baseline_iters=args.baseline_iters,
                   baseline_calls_per_window=args.baseline_calls, sizes=results)
     lines.append(json.dumps(result))
-    print(lines[-1], flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    emit(lines, args.out, printed=len(lines) - 1)
 
 
 if __name__ == "__main__":
