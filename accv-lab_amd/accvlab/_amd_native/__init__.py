@@ -94,6 +94,10 @@ VX_MIN_D = 3
 VX_MAX_D = 16
 VX_MAX_POINTS = 128
 VX_MAX_VOXELS = 1 << 20
+PF_CLUSTER = 1
+PF_CENTER = 2
+PF_DISTANCE = 4
+BS_MAX_C = 1024
 VB_MAX_BOXES = 256
 VB_COUNTS_I64 = 1
 VB_HW_I64 = 2
@@ -269,6 +273,18 @@ SIGNATURES = {
     "accv_voxelize_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll, _ll]),
     "accv_voxelize": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "accv_voxelize_cpu": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+    # pillar decoration (params: a PillarFeaturesParams by address; out [M, T, F]) and the voxel mean (out [M, num_features]);
+    # the host entries end in _cpu
+    "accv_pillar_features": (_i, [_vp, _ll, _ll, _ll, _vp, _vp]),
+    "accv_pillar_features_cpu": (_i, [_vp, _ll, _ll, _ll, _vp]),
+    "accv_voxel_mean": (_i, [_vp, _vp, _ll, _ll, _ll, _ll, _vp, _vp]),
+    "accv_voxel_mean_cpu": (_i, [_vp, _vp, _ll, _ll, _ll, _ll, _vp]),
+    # BEV scatter (canvas [B, C, ny, nx], index [B, ny, nx]) and its backward (grad_features [rows, C]); the host entries
+    # end in _cpu
+    "accv_bev_scatter": (_i, [_vp, _vp, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _vp, _vp, _vp]),
+    "accv_bev_scatter_cpu": (_i, [_vp, _vp, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _vp, _vp]),
+    "accv_bev_scatter_bwd": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _vp, _vp]),
+    "accv_bev_scatter_bwd_cpu": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _vp]),
     # H3 multi-tensor copier
     "accv_mtc_plan": (_i, [_ll, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "accv_pinned_acquire": (_vp, [_sz]),
@@ -466,6 +482,13 @@ class VoxelizeParams(ctypes.Structure):
                 ("sizes_i64", ctypes.c_int)]
 
 
+class PillarFeaturesParams(ctypes.Structure):
+    """accv_pillar_features_params of include/accv_hip.h"""
+    _fields_ = [("voxels", ctypes.c_void_p), ("num_points", ctypes.c_void_p), ("coors", ctypes.c_void_p),
+                ("voxel_size", ctypes.c_double * 3), ("range_min", ctypes.c_double * 3), ("coor_width", ctypes.c_int),
+                ("flags", ctypes.c_uint)]
+
+
 _lib = None
 _handle = None
 
@@ -485,7 +508,9 @@ _BLOCKING = {name for name in SIGNATURES if name.endswith("_host")} | {"accv_mtc
 # stay on ctypes too
 HOST_ENTRY_NAMES = {"accv_box_decode": "accv_box_decode_cpu", "accv_box_nms": "accv_box_nms_cpu",
                     "accv_query_decode_3d": "accv_query_decode_3d_cpu", "accv_query_decode_2d": "accv_query_decode_2d_cpu",
-                    "accv_depth_targets": "accv_depth_targets_cpu", "accv_voxelize": "accv_voxelize_cpu"}
+                    "accv_depth_targets": "accv_depth_targets_cpu", "accv_voxelize": "accv_voxelize_cpu",
+                    "accv_pillar_features": "accv_pillar_features_cpu", "accv_voxel_mean": "accv_voxel_mean_cpu",
+                    "accv_bev_scatter": "accv_bev_scatter_cpu", "accv_bev_scatter_bwd": "accv_bev_scatter_bwd_cpu"}
 _CTYPES_ONLY = _BLOCKING | set(HOST_ENTRY_NAMES.values())
 
 

@@ -1146,6 +1146,72 @@ int accv_voxelize(const accv_voxelize_params* params, long long B, long long P, 
 int accv_voxelize_cpu(const accv_voxelize_params* params, long long B, long long P, long long D, float* voxels, int* coors,
                       int* num_points, int* voxel_counts, int* point_voxel);
 
+/* ------------------------------------------------------------------------------- pillar decoration and the voxel mean
+ * From the voxels of accv_voxelize to the rows a pillar feature net's first linear layer reads: mmdet3d's non-legacy
+ * PillarFeatureNet.forward up to that layer (accv_pillar_features) and HardSimpleVFE (accv_voxel_mean), one launch each.
+ *
+ * voxels [M, T, D] f32 contiguous, ACCV_VX_MIN_D <= D <= ACCV_VX_MAX_D, 1 <= T <= ACCV_VX_MAX_POINTS; num_points [M] int32,
+ * clamped to [0, T]; coors [M, coor_width] int32 with coor_width 3 (z, y, x) or 4 (b, z, y, x): the last three columns are
+ * read.  voxel_size > 0 and range_min finite, rounded to float32 once.  Per voxel, float32, nothing contracted
+ * (csrc/pillar_features_arith.h):
+ *   n = clamp(num_points, 0, T);  s_k = ((p_0k + p_1k) + p_2k) + ... over the rows j < n in row order, k = x, y, z
+ *   mean_k = s_k / float(n);  centre_k = float(c_k) * v_k + (v_k * 0.5f + lo_k), c = (x, y, z) from the last coors columns
+ *   a row j < n: [the D input channels bit for bit | p_jk - mean_k (ACCV_PF_CLUSTER) | p_jk - centre_k (ACCV_PF_CENTER) |
+ *   sqrt((x * x + y * y) + z * z) (ACCV_PF_DISTANCE)];  a row j >= n: +0.0 in every channel, whatever the input holds there
+ * out f32 [M, T, F], F = D + 3 per CLUSTER and CENTER + 1 for DISTANCE, every element written exactly once.
+ * accv_voxel_mean: out f32 [M, num_features], the same s_k / float(n) over the first 1 <= num_features <= D channels, +0.0
+ * where n == 0.  Device: one launch on `stream`; a workgroup stages as many consecutive voxels as fit its LDS budget (16-byte
+ * loads where the voxels and the workgroup's range are 16-byte aligned), sums from LDS, a lane per (voxel, channel), and all
+ * lanes write the rows; no workspace, no atomics, nothing read but the three inputs.  M == 0 launches nothing.  ACCV_EINVAL
+ * (null params, sizes or scalars outside the ranges above, null or misaligned pointers) before touching the data,
+ * ACCV_ELAUNCH if the launch fails.  The _cpu entries evaluate the same arithmetic on host memory. */
+#define ACCV_PF_CLUSTER 1u
+#define ACCV_PF_CENTER 2u
+#define ACCV_PF_DISTANCE 4u
+typedef struct accv_pillar_features_params {
+    const float* voxels;
+    const int* num_points;
+    const int* coors;
+    double voxel_size[3];           /* x, y, z */
+    double range_min[3];
+    int coor_width;                 /* 3 or 4 */
+    unsigned flags;                 /* ACCV_PF_* */
+} accv_pillar_features_params;
+int accv_pillar_features(const accv_pillar_features_params* params, long long M, long long T, long long D, float* out, void* stream);
+int accv_pillar_features_cpu(const accv_pillar_features_params* params, long long M, long long T, long long D, float* out);
+int accv_voxel_mean(const float* voxels, const int* num_points, long long M, long long T, long long D, long long num_features,
+                    float* out, void* stream);
+int accv_voxel_mean_cpu(const float* voxels, const int* num_points, long long M, long long T, long long D, long long num_features,
+                        float* out);
+
+/* ------------------------------------------------------------------------------------------------------- BEV scatter
+ * From per-pillar features to the dense map a 2D backbone convolves: mmdet3d's PointPillarsScatter for the whole batch, the
+ * canvas written once with its zeros, and the backward of that.
+ *
+ * features [rows, C] of elem_size 4 (f32) or 2 (f16 / bf16: the copy moves bits), contiguous, 1 <= C <= ACCV_BS_MAX_C;
+ * coors int32 [rows, coor_width]: coor_width 4 is (b, z, y, x); coor_width 3 is (z, y, x) with the frame implicit, b = r / V
+ * (the padded [B, V, ...] form, rows == B * V).  Row r is placed iff 0 <= b < B, 0 <= y < ny, 0 <= x < nx; z is ignored.
+ * B * ny * nx < 2^31, rows < 2^31.
+ *   index [B, ny, nx] int32: the highest placed r of the cell, or -1
+ *   canvas [B, C, ny, nx]: features[index[b, y, x], c], or +0 where the index is -1; every element written exactly once
+ *   backward: grad_features[r, c] = grad_canvas[b, c, y, x] if index[cell(r)] == r, else +0; every element written once
+ * Device, forward: one hipMemsetAsync (index = 0xFF bytes) and two launches on `stream`: mark (a lane per row, atomicMax on
+ * index) and write (a workgroup per frame, map row, 64 cells along x and 64 channels: the occupied cells' feature rows through
+ * LDS, 16-byte loads and stores where features, canvas, C * elem_size and nx * elem_size are 16-byte aligned, element by
+ * element otherwise; a tile without rows stores zeros only).  No atomic on the canvas and no read of it.  Backward: one
+ * launch, no atomics; reads coors, index and grad_canvas.  B == 0 launches nothing; rows == 0 still writes canvas and
+ * index.  ACCV_EINVAL (sizes outside the ranges above, null or misaligned pointers) before touching the data, ACCV_ELAUNCH
+ * if a launch fails.  The _cpu entries run the sequential loop on host memory. */
+#define ACCV_BS_MAX_C 1024
+int accv_bev_scatter(const void* features, const int* coors, long long rows, long long V, long long B, long long C, long long ny,
+                     long long nx, int coor_width, int elem_size, void* canvas, int* index, void* stream);
+int accv_bev_scatter_cpu(const void* features, const int* coors, long long rows, long long V, long long B, long long C, long long ny,
+                         long long nx, int coor_width, int elem_size, void* canvas, int* index);
+int accv_bev_scatter_bwd(const void* grad_canvas, const int* coors, const int* index, long long rows, long long V, long long B,
+                         long long C, long long ny, long long nx, int coor_width, int elem_size, void* grad_features, void* stream);
+int accv_bev_scatter_bwd_cpu(const void* grad_canvas, const int* coors, const int* index, long long rows, long long V, long long B,
+                             long long C, long long ny, long long nx, int coor_width, int elem_size, void* grad_features);
+
 /* ------------------------------------------------------------------------------------------------ batched assignment
  * Replaces the per-frame scipy.optimize.linear_sum_assignment loop of the Hungarian matcher
  * (packages/batching_helpers/example/matcher.py:52-74: cost.to_device(cpu), split, scipy per frame, combine_data, copy
