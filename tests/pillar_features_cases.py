@@ -256,6 +256,94 @@ def check_guard_bands(dev, max_group, lds_floats):
             assert_bits(out.clone(), want, f"banded {name}, T {T}, D {D}, shift {shift}")
 
 
+# (T, D, flags, G * T * D % 4 == 0, G * T * F % 4 == 0) with G from the device's constants (64, 8192): the smallest shapes at
+# which a workgroup's own range, not a base address, is the reason for 4-byte loads, 4-byte stores, or either alone
+DISPATCH = [(43, 3, (False, False, False), False, False),       # G 63, F 3: G T D = G T F = 8127
+            (43, 3, (False, False, True), False, True),         # G 63, F 4: loads 4-byte, stores 16-byte
+            (43, 4, (True, False, False), True, False)]         # G 47, F 7: G T D = 8084, G T F = 14147
+DISPATCH_MEAN = (43, 3, (1, 3))
+
+
+def feature_count(D, flags):
+    return D + 3 * flags[0] + 3 * flags[1] + flags[2]
+
+
+def check_dispatch(dev, max_group, lds_floats):
+    """both tensors 16-byte aligned and G * T * D or G * T * F no multiple of 4: from the second workgroup on the range of
+    a workgroup starts off a 16-byte boundary, which is what sends the launch to its 4-byte loads or stores (all three
+    mixed instantiations of the decoration, and the 4-byte voxel mean on an aligned input).  Through the operators at
+    M in {G - 1, G, G + 1, 2 G + 1} against the definition (and the host entry when `dev` is a GPU), then through the C
+    entries alone into guard-banded, 16-byte aligned outputs: the 4-byte store path has no vector tail to hide an overrun"""
+    from accvlab import _amd_native as nat
+
+    lib = nat.ctypes_lib()
+    cuda = torch.device(dev).type == "cuda"
+    stream = nat.stream_ptr(torch.device(dev, torch.cuda.current_device())) if cuda else None
+    pad = 512
+
+    def banded(shape):
+        nbytes = 4 * int(np.prod(shape))
+        buf = torch.full((pad + nbytes + pad,), 0xA5, dtype=torch.uint8, device=dev)
+        out = buf[pad: pad + nbytes].view(torch.float32).view(shape)
+        assert out.data_ptr() % 16 == 0, "the banded output is not 16-byte aligned"
+        return buf, out, nbytes
+
+    def intact(buf, nbytes):
+        if cuda:
+            torch.cuda.synchronize()
+        return bool((buf[:pad] == 0xA5).all()) and bool((buf[pad + nbytes:] == 0xA5).all())
+
+    for T, D, flags, in_by_4, out_by_4 in DISPATCH:
+        G, F = group_of(T, D, max_group, lds_floats), feature_count(D, flags)
+        assert ((G * T * D) % 4 == 0, (G * T * F) % 4 == 0) == (in_by_4, out_by_4), f"T {T}, D {D}, {flags}: G {G} is not the regime"
+        counts = sorted({G - 1, G, G + 1, 2 * G + 1})
+        assert counts[-2] > G, "no workgroup with a base off a 16-byte boundary"
+        for M in counts:
+            what = f"dispatch T {T}, D {D}, flags {flags}, M {M}"
+            vox, num, coors = make_voxels(3000 + 10 * D + M % 7, M, T, D)
+            tv, tn, tc = to_dev(dev, vox, num, coors)
+            assert tv.data_ptr() % 16 == 0, f"{what}: voxels are not 16-byte aligned"
+            got = pillar_features(tv, tn, tc, **flag_kw(flags), **GRID)
+            assert got.data_ptr() % 16 == 0 and tuple(got.shape) == (M, T, F), f"{what}: the output is not 16-byte aligned"
+            want = definition(vox, num, coors, **flag_kw(flags), **GRID)
+            assert_bits(got, want, what)
+            if cuda:
+                assert_bits(got, pillar_features(*to_dev("cpu", vox, num, coors), **flag_kw(flags), **GRID), what + ", host entry")
+            p = nat.PillarFeaturesParams()
+            p.voxels, p.num_points, p.coors = tv.data_ptr(), tn.data_ptr(), tc.data_ptr()
+            p.voxel_size[:], p.range_min[:] = GRID["voxel_size"], GRID["point_cloud_range"][:3]
+            p.coor_width = 4
+            p.flags = (nat.PF_CLUSTER if flags[0] else 0) | (nat.PF_CENTER if flags[1] else 0) | (nat.PF_DISTANCE if flags[2] else 0)
+            buf, out, nbytes = banded((M, T, F))
+            args = (ctypes.addressof(p), M, T, D, out.data_ptr())
+            status = lib.accv_pillar_features(*args, stream) if cuda else lib.accv_pillar_features_cpu(*args)
+            assert status == 0, lib.accv_last_error()
+            assert intact(buf, nbytes), f"{what}: wrote outside features"
+            assert_bits(out.clone(), want, what + ", banded")
+
+    T, D, widths = DISPATCH_MEAN
+    G = group_of(T, D, max_group, lds_floats)
+    assert (G * T * D) % 4 != 0
+    for M in sorted({G - 1, G, G + 1, 2 * G + 1}):
+        vox, num, _ = make_voxels(3100 + M % 7, M, T, D)
+        clean = mean_input(vox, num)
+        tm, tn = to_dev(dev, clean, num)
+        assert tm.data_ptr() % 16 == 0
+        for nf in widths:
+            what = f"dispatch mean T {T}, D {D}, M {M}, nf {nf}"
+            got, want = voxel_mean(tm, tn, num_features=nf), mean_definition(clean, num, nf)
+            assert got.data_ptr() % 16 == 0
+            assert_bits(got, want, what)
+            if cuda:
+                assert_bits(got, voxel_mean(*to_dev("cpu", clean, num), num_features=nf), what + ", host entry")
+            buf, out, nbytes = banded((M, nf))
+            args = (tm.data_ptr(), tn.data_ptr(), M, T, D, nf, out.data_ptr())
+            status = lib.accv_voxel_mean(*args, stream) if cuda else lib.accv_voxel_mean_cpu(*args)
+            assert status == 0, lib.accv_last_error()
+            assert intact(buf, nbytes), f"{what}: wrote outside mean"
+            assert_bits(out.clone(), want, what + ", banded")
+
+
 def mmdet3d_forward(features, num_points, coors, voxel_size, point_cloud_range, with_distance):
     """mmdet3d's non-legacy PillarFeatureNet.forward up to its PFN layers, in torch"""
     vx_, vy, vz = voxel_size

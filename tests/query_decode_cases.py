@@ -35,7 +35,13 @@ HW = (96, 160)
 
 
 def _np32(t):
-    return t.detach().cpu().float().numpy()
+    """float32 numpy values of a tensor, f16 / bf16 widened exactly.  float16 goes through numpy: torch's CPU cast turns every
+    float16 NaN into 0x7FFFFFFF, while the operators (csrc/accv_numeric.h) and numpy keep its sign and payload, and a raw
+    score is a copy of the value"""
+    t = t.detach().cpu()
+    if t.dtype == torch.float16:
+        return t.contiguous().view(torch.int16).numpy().view(np.float16).astype(np.float32)
+    return t.float().numpy()
 
 
 def order_key(x):
@@ -306,6 +312,28 @@ def run(op, definition, cls, rows, max_num, **kw):
     want = definition(cls, rows, max_num, **host)
     assert_margin(want, kw.get("score_threshold"))
     return got, want
+
+
+def check_raw_half_nan(op3, op2, dev):
+    """raw scores (scores_are_logits=False) of float16 / bfloat16 logits with NaNs of several signs and payloads, all of which
+    rank first: the score is the value widened exactly, a NaN with its sign and payload.  (The sweeps of DESIGN §9zg found
+    that `_np32` widened through torch's CPU cast, which gives 0x7FFFFFFF for every float16 NaN.)  Quiet NaNs only: a
+    conversion instruction may quiet a signalling one."""
+    B, Q, C = 2, 40, 3
+    for dtype, quiet, widened in ((torch.float16, [0x7E00, 0x7E12, 0xFE01], [0x7FC00000, 0x7FC24000, 0xFFC02000]),
+                                  (torch.bfloat16, [0x7FC0, 0x7FC1, 0xFFC3], [0x7FC00000, 0x7FC10000, 0xFFC30000])):
+        cls = logits(B, Q, C, "distinct", dtype=dtype, seed=5)
+        words = cls.view(torch.int16).view(B, -1)
+        at = [7, 50, 119]
+        words[:, at] = torch.tensor(quiet, dtype=torch.int32).to(torch.int16)
+        cls = cls.to(dev)
+        for M in (2, Q * C):
+            got, want = run(op3, definition_3d, cls, rows_3d(B, Q, 10, seed=5).to(dev), M, scores_are_logits=False)
+            check(got, want, f"3d raw {dtype} M={M}")
+            assert want["score_exact"].view(np.uint32)[0, :min(M, 3)].tolist() == widened[:min(M, 3)], "the case holds no NaN payload"
+            assert got.source.tensor[0, :min(M, 3)].tolist() == [a // C for a in at][:min(M, 3)]
+            got, want = run(op2, definition_2d, cls, rows_2d(B, Q, seed=5).to(dev), M, image_hw=HW, scores_are_logits=False)
+            check(got, want, f"2d raw {dtype} M={M}")
 
 
 def max_nums(N, limit=1024):

@@ -48,6 +48,10 @@ def test_guard_bands_and_complete_write_through_the_c_entries_alone():
     cases.check_guard_bands(DEV, MAX_GROUP, LDS_FLOATS)
 
 
+def test_workgroup_ranges_off_a_16_byte_boundary_under_aligned_tensors():
+    cases.check_dispatch(DEV, MAX_GROUP, LDS_FLOATS)
+
+
 def test_against_the_torch_composition_of_mmdet3d():
     cases.check_against_torch(DEV)
 

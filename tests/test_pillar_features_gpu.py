@@ -61,6 +61,13 @@ def test_guard_bands_and_complete_write_through_the_c_entries_alone():
     cases.check_guard_bands(DEV, MAX_GROUP, LDS_FLOATS)
 
 
+def test_workgroup_ranges_off_a_16_byte_boundary_under_aligned_tensors():
+    """the three mixed instantiations of the decoration and the 4-byte voxel mean, entered by divisibility alone"""
+    assert "const bool vec_in = (addr(a.voxels) & 15u) == 0 && ((long long)a.G * a.T * a.D) % 4 == 0;" in _SRC
+    assert "const bool vec_out = (addr(a.out) & 15u) == 0 && ((long long)a.G * a.T * a.F) % 4 == 0;" in _SRC
+    cases.check_dispatch(DEV, MAX_GROUP, LDS_FLOATS)
+
+
 def test_against_the_torch_composition_of_mmdet3d():
     cases.check_against_torch(DEV)
 

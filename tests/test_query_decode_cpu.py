@@ -66,6 +66,10 @@ def test_half_precision_scores_and_rows(dtype, row_dtype):
             assert len(np.unique(qc._np32(cls))) < cls.numel(), "the cast leaves no tie: the case shows nothing about them"
 
 
+def test_raw_half_precision_scores_keep_the_sign_and_payload_of_a_nan():
+    qc.check_raw_half_nan(op3, op2, "cpu")
+
+
 def test_the_cut_falls_inside_a_tie_group_and_equal_logits_come_in_index_order():
     cls = logits(2, 50, 10, "two", seed=4)
     high = int((cls[0] > 0).sum())

@@ -136,6 +136,14 @@ def test_half_precision_scores_and_rows(dtype, row_dtype):
         both(op2, definition_2d, cls, rows_2d(B, Q, dtype=row_dtype, seed=2), 300, f"2d {dtype} {row_dtype} {kind}", image_hw=HW, score_threshold=THR)
 
 
+def test_raw_half_precision_scores_keep_the_sign_and_payload_of_a_nan():
+    import query_decode_cases as qc
+
+    qc.check_raw_half_nan(op3, op2, DEV)
+    cls = logits(2, 40, 3, "special", dtype=torch.float16, seed=5)
+    both(op3, definition_3d, cls, rows_3d(2, 40, 10, seed=5), 120, "raw float16 special", scores_are_logits=False)
+
+
 def test_frames_with_no_valid_row_and_with_every_row_valid():
     cls = logits(3, 130, 10, seed=2)
     cls[0] -= 20.0
